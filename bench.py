@@ -5,8 +5,8 @@ A "step" is one outer registration iteration over one source/target pair:
     radius-NN association (K1) -> t/Gaussian weights + weighted moments (K23) -> 3x3 SVD -> in-place move of
     the source (K4, folded into the next K1),
 i.e. BASELINE.json's metric "registration iterations/sec (1M<->1M pts, r=1.0, m=10)" with one inner IRLS step per
-association, early termination disabled (cost_drop_thresh = 0).  Clouds are resident in HBM
-before a timed window starts.
+association, early termination disabled (cost_drop_thresh = -1: exactly --steps iterations, converged
+or not).  Clouds are resident in HBM before a timed window starts.
 
 Timed region: `--windows` (default 5) windows; every window re-uploads the source (fresh start), runs `--warmup`
 untimed iterations, and then times EXACTLY `--steps` iterations between barrier + synchronize on both sides (max over
@@ -19,6 +19,11 @@ line never reports an n_gpus other than the one asked for.
   config 5 (BASELINE configs[4]): 64 pairs of 250k, 64 / N per rank (strong scaling), the gathered transforms
   checked on rank 0 against a single-rank run of every pair.
 The only collective of the job is the final all_gather of the transforms over RCCL, inside the timed window.
+
+A plain run sets up, settles, runs the timed windows and prints the line.  --full adds, after the windows, everything else
+the benchmark measures or checks (per-kernel / roofline passes, set-up cost, cold start, converged inner loop, steady state,
+time to converge, the C++ API block, the command line's default shapes, the batch verification, CPU baselines and parity).
+--dump-outputs DIR writes what the last window's timed call returned as DIR/<name>.npy.
 
 Prints ONE JSON line on rank 0.
 """
@@ -57,6 +62,17 @@ def parse():
     ap.add_argument("--inner-steps", type=int, default=None,
                     help="IRLS steps per association (default 1: the metric's definition; config 8 = the command line's own "
                          "defaults: 100, to function_tolerance)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed windows also run everything else the benchmark measures or checks (per-kernel and "
+                         "roofline passes, set-up cost, cold start, converged inner loop, steady state, time to converge, "
+                         "the C++ API block, the command line's default shapes, the batch verification, the CPU baselines "
+                         "and parity); the --no-* switches below narrow such a run.  Without it: set-up, warm-up, the timed "
+                         "windows, --dump-outputs, the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed windows write what the last window's timed call returned as DIR/<name>.npy "
+                         "(float64): transforms (pairs x 3 x 4, the gathered final transforms) and, where every pair "
+                         "runs through align(), history (pairs x steps x 3 x 4), costs (pairs x steps x 2) and "
+                         "inner_steps (pairs x steps)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-iters", type=int, default=0,
                     help="outer iterations of the CPU baseline sample (0 = auto: about 6 s of wall time, 3..30)")
@@ -243,7 +259,7 @@ def cpp_api_block(src, tgt, cfg, a):
     exe = os.path.join(ROOT, "probabilistic_point_clouds_registration_amd", "ppcr_cpp_api_test")
     if not os.path.exists(exe):
         return {"error": "ppcr_cpp_api_test is not built (python -m probabilistic_point_clouds_registration_amd.build)"}
-    block = {"program": "ppcr_cpp_api_test --bench (ProbPointCloudRegistration::align(), cost_drop_thresh = 0)",
+    block = {"program": "ppcr_cpp_api_test --bench (ProbPointCloudRegistration::align(), cost_drop_thresh = -1)",
              "method": "steady it/s = S / (align time of warm + S iterations - align time of warm iterations), S = 3 x steps, "
                        "a fresh object per measurement (all constructed before the first is timed), median of 7"}
     with tempfile.TemporaryDirectory(prefix="ppcr_bench_") as d:
@@ -324,8 +340,22 @@ def fake_align_many(ctxs, k, lanes=1, **kw):
     return np.array(out), [k] * len(ctxs)
 
 
+def dump_outputs(path, gathered, results):
+    """--dump-outputs: the arrays the last window's timed call handed back, one .npy each (float64).  The clouds are pinned
+    by the arguments (synth's seeds), so two builds run with the same arguments can be compared output for output."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "transforms.npy"), np.ascontiguousarray(gathered, dtype=np.float64))
+    if results:   # (pairs that went through align(): this rank's, in pair order)
+        res = [results[p] for p in sorted(results)]
+        for name in ("history", "costs", "inner_steps"):
+            np.save(os.path.join(path, name + ".npy"), np.stack([np.asarray(r[name], dtype=np.float64) for r in res]))
+
+
 def run_rank(a):
     from probabilistic_point_clouds_registration_amd import batch, synth
+    if not a.full:
+        # a plain run does what the headline figure needs and nothing else
+        a.no_profile = a.no_extras = a.no_cpu_baseline = a.no_cpp_api = a.no_verify = True
     if a.fake_register:
         import types
         _lib = types.SimpleNamespace(Context=FakeContext, align_many=fake_align_many)
@@ -401,13 +431,16 @@ def run_rank(a):
         if dist is not None:
             dist.barrier()
 
-    # with the inner loop run to function_tolerance a pair converges inside the window and its cost drop becomes rounding
-    # noise of either sign: those workloads run their k iterations regardless of it
-    timed_thresh = -1.0 if a.inner_steps > 1 else 0.0
+    # --steps sets the number of timed iterations, whatever it is: a pair that converges inside the window (a long one, or
+    # the inner loop run to function_tolerance) has a cost drop of rounding noise of either sign, so the stopping rule's
+    # threshold is negative — the rule only decides when the loop ends, never what an iteration computes
+    timed_thresh = -1.0
+
+    last_results = {}   # pair -> what the latest align() of run_iterations returned (--dump-outputs)
 
     def run_iterations(k, inner, f_tol=1e-5, thresh=None):
         """k outer iterations on every pair of this rank -> {pair: final cumulative 3x4 of these k iterations}
-        (thresh = 0 runs exactly k iterations while the cost still falls; a converged pair, whose cost drop is rounding
+        (thresh = 0 would run k iterations only while the cost still falls; a converged pair, whose cost drop is rounding
         noise of either sign, needs a negative threshold to keep going)"""
         out = {}
         thresh = timed_thresh if thresh is None else thresh
@@ -422,6 +455,7 @@ def run_rank(a):
                 res = c.align(k, cost_drop_thresh=thresh, inner_steps=inner, f_tol=f_tol)
                 assert res["n_iter"] == k, f"early stop: {res['n_iter']}"
                 out[p] = res["history"][-1] if k > 0 else np.eye(4)[:3]
+                last_results[p] = res
         return out
 
     def fresh_start(inner, f_tol=1e-5):
@@ -440,9 +474,10 @@ def run_rank(a):
     if a.settle_ms > 0:
         fresh_start(a.inner_steps)
         ts = time.perf_counter()
+        chunk = min(max(a.steps, 50), 1000)   # (a long window is not settled by one more whole window)
         while (time.perf_counter() - ts) * 1e3 < a.settle_ms:
-            run_iterations(max(a.steps, 50), a.inner_steps, thresh=-1.0)
-            settle_iters += max(a.steps, 50)
+            run_iterations(chunk, a.inner_steps, thresh=-1.0)
+            settle_iters += chunk
         barrier()
 
     # ---- timed windows --------------------------------------------------------------------------------------------
@@ -465,6 +500,8 @@ def run_rank(a):
     if dist is None:
         gathered = batch.gather_transforms(local, n_pairs)
     dt = float(np.median(window_s))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, gathered, last_results)
 
     # ---- per-kernel durations with HIP events on the handle's own stream (separate passes so that the event records
     # cannot perturb the headline number; same workload, same warm-up, same K).  Pass A is the schedule of the timed
@@ -569,7 +606,7 @@ def run_rank(a):
                                + (f"batch of {n_pairs} independent pairs of " if n_pairs > 1 else "")
                                + f"{ns}<->{nt} synthetic clouds, radius={cfg['radius']}, "
                                f"max_neighbours={cfg['max_neighbours']}, {model}, "
-                               f"{a.inner_steps} inner IRLS step(s)/iteration, cost_drop_thresh=0",
+                               f"{a.inner_steps} inner IRLS step(s)/iteration, cost_drop_thresh=-1 (no early stop)",
                    "pairs": n_pairs, "pairs_per_gpu": pairs_per_gpu, "lanes_per_gpu": (a.lanes if concurrent else 1),
                    "parallelism": f"{n_pairs} independent pair(s), {pairs_per_gpu} per GPU on {world} GPU(s); "
                                   "no data-path collective; final RCCL all_gather of the transforms"},
@@ -688,7 +725,7 @@ def run_rank(a):
             tc = time.perf_counter()
             res = ctx.align(a.steps, cost_drop_thresh=0.0, inner_steps=100, f_tol=REF_F_TOL)
             ctx.synchronize()
-            rates.append(a.steps / (time.perf_counter() - tc))
+            rates.append(int(res["n_iter"]) / (time.perf_counter() - tc))   # (the reference's rule may end a long run early)
             inner_mean = float(np.mean(res["inner_steps"]))
         out["converged_inner"] = {"it_per_s": float(np.median(rates)), "ms_per_iteration": 1e3 / float(np.median(rates)),
                                   "min_it_per_s": min(rates), "max_it_per_s": max(rates),
@@ -780,14 +817,14 @@ def run_rank(a):
                                       "schedule": "host buffers in; the CLI's defaults for the stopping rule (-c 0.01 -n 5, "
                                                   "<= 1000 iterations) and the inner loop (<= 100 IRLS steps, f_tol 1e-5); warm handle"}
         # the drop-in surface itself: ProbPointCloudRegistration::align() (one call into ppcr_align_report) timed in a
-        # child process running the C++ API test program on the same clouds: -c 0 -i (warmup + steps), once with one
+        # child process running the C++ API test program on the same clouds: -c -1 -i (warmup + steps), once with one
         # inner step per association, once with the class's default (inner loop to function_tolerance)
         if not a.no_cpp_api and not batch_cfg:
             out["cpp_api"] = cpp_api_block(src, tgt, cfg, a)
 
     if world == 1 and a.config == 3 and not a.no_extras and not a.fake_register and a.n is None:
         # The reference's OWN defaults (prob_point_cloud_registration_ex.cc:43-56: radius 3, 20 neighbours, inner loop to
-        # function_tolerance) beside the headline, so that every default run times them: bench.py --config 8 / 9 / 10 in
+        # function_tolerance) beside the headline, so that every --full default run times them: bench.py --config 8 / 9 / 10 in
         # short — a uniform 200k cloud (two-pass search) and the two pinned non-uniform scenes (multi-level search); three
         # windows of `steps` iterations each after a settle phase, median, same timing rules as `value`.
         shapes = {}

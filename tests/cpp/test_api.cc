@@ -522,7 +522,7 @@ static int benchMain(int argc, char **argv)
     const int warm = std::atoi(argv[7]), steps = std::atoi(argv[8]);
     params.inner_max_steps = std::atoi(argv[9]);
     const int repeats = argc > 10 ? std::atoi(argv[10]) : 5;
-    params.cost_drop_thresh = 0;  // -c 0: exactly n_iter iterations
+    params.cost_drop_thresh = -1;  // exactly n_iter iterations, also once the registration has converged (-c 0 stops there)
     // every object is constructed (clouds uploaded) before anything is timed, and the align() calls then run back to
     // back: the device does not idle (and clock down) through uploads between two measurements
     std::vector<double> construct_s;

@@ -38,7 +38,7 @@ def test_world_size_mismatch_is_refused():
 def test_bench_line_has_the_agreed_blocks():
     """A small run of the real thing (20k points, RCCL initialised with one rank): one JSON line with the median-of-
     windows value, roofline + traffic source, both CPU baselines, cold-start times, the converged-inner block and parity."""
-    r = _run(["--n", "20000", "--steps", "4", "--warmup", "2", "--windows", "3", "--force-dist", "--cpu-iters", "3"])
+    r = _run(["--full", "--n", "20000", "--steps", "4", "--warmup", "2", "--windows", "3", "--force-dist", "--cpu-iters", "3"])
     assert r.returncode == 0, r.stdout + r.stderr
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(line) == 1
@@ -73,11 +73,63 @@ def test_launcher_counts_devices_without_the_hip_runtime():
     assert int(r.stdout.strip()) >= 0
 
 
+def test_dump_outputs_writes_the_last_windows_arrays(tmp_path):
+    """--dump-outputs on the rank logic's CPU stand-in: float64 arrays of the last timed call, shaped by --steps, equal
+    from run to run; a plain line carries the headline fields and none of the --full blocks."""
+    import numpy as np
+    dumps = []
+    for d in ("a", "b"):
+        r = _run(["--gpus", "1", "--points", "300", "--steps", "3", "--warmup", "1", "--windows", "2", "--backend", "gloo",
+                  "--fake-register", "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stdout + r.stderr
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in out
+        assert out["steps"] == 3 and abs(out["ms_per_step"] * 3 - out["windows"]["window_ms"]) < 1e-9
+        for key in ("cpu_baseline", "parity", "converged_inner", "setup_ms", "cpp_api", "cli_default_shapes"):
+            assert key not in out
+        dumps.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    assert sorted(dumps[0]) == ["costs.npy", "history.npy", "inner_steps.npy", "transforms.npy"]
+    assert dumps[0]["transforms.npy"].shape == (1, 3, 4) and dumps[0]["history.npy"].shape == (1, 3, 3, 4)
+    assert np.array_equal(dumps[0]["history.npy"][0, -1], dumps[0]["transforms.npy"][0])
+    for f, arr in dumps[0].items():
+        assert arr.dtype == np.float64 and np.array_equal(arr, dumps[1][f])
+
+
+@pytest.mark.gpu
+def test_gpu_dump_outputs_of_a_plain_run(tmp_path):
+    """The real thing at 20k points: a plain run writes the last window's transforms and per-iteration history."""
+    import numpy as np
+    r = _run(["--n", "20000", "--steps", "4", "--warmup", "2", "--windows", "2", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stdout + r.stderr
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 4 and out["ms_per_step"] > 0 and "cpu_baseline" not in out and "parity" not in out
+    T, hist = np.load(tmp_path / "transforms.npy"), np.load(tmp_path / "history.npy")
+    assert T.shape == (1, 3, 4) and hist.shape == (1, 4, 3, 4) and T.dtype == hist.dtype == np.float64
+    assert np.array_equal(hist[0, -1], T[0]) and np.isfinite(hist).all()
+    assert np.load(tmp_path / "costs.npy").shape == (1, 4, 2) and np.load(tmp_path / "inner_steps.npy").shape == (1, 4)
+    # a rigid transform came out: R^T R = 1 to rounding
+    assert np.abs(T[0][:, :3].T @ T[0][:, :3] - np.eye(3)).max() < 1e-12
+
+
+@pytest.mark.gpu
+def test_steps_past_convergence_are_all_timed(tmp_path):
+    """--steps sets the number of timed iterations also where the pair converges long before the window ends (with a
+    stopping threshold of 0 the rule ended such a window after some 400 iterations): 1500 steps, 1500 rows of history."""
+    import numpy as np
+    r = _run(["--n", "20000", "--steps", "1500", "--warmup", "2", "--windows", "2", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stdout + r.stderr
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 1500 and abs(out["ms_per_step"] * 1500 - out["windows"]["window_ms"]) < 1e-9
+    hist = np.load(tmp_path / "history.npy")
+    assert hist.shape == (1, 1500, 3, 4) and np.isfinite(hist).all()
+
+
 @pytest.mark.gpu
 def test_config5_batch_line_small():
     """--config 5 shape at a reduced size: 64 pairs on the one GPU of the test box, every gathered transform verified
     against its single-rank run inside bench.py itself."""
-    r = _run(["--config", "5", "--n", "6000", "--steps", "3", "--warmup", "1", "--windows", "2", "--no-cpu-baseline",
+    r = _run(["--full", "--config", "5", "--n", "6000", "--steps", "3", "--warmup", "1", "--windows", "2", "--no-cpu-baseline",
               "--no-extras"])
     assert r.returncode == 0, r.stdout + r.stderr
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])

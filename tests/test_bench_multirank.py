@@ -38,7 +38,7 @@ def _line(r):
 
 
 def test_config5_two_ranks_shard_gather_verify_and_leave_together():
-    out = _line(_torchrun(2, ["--gpus", "2", "--config", "5", "--points", "300", "--steps", "3", "--warmup", "1", "--windows", "2",
+    out = _line(_torchrun(2, ["--full", "--gpus", "2", "--config", "5", "--points", "300", "--steps", "3", "--warmup", "1", "--windows", "2",
                               "--backend", "gloo", "--fake-register"]))
     assert out["n_gpus"] == 2 and out["scaling"] == "strong"
     assert out["config"]["pairs"] == 64 and out["config"]["pairs_per_gpu"] == 32

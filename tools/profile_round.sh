@@ -9,7 +9,7 @@ set -u; R=${GRAFT_REPO_ROOT:?GRAFT_REPO_ROOT not set}
 OUT=$R/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $R/bench.py --no-cpu-baseline --no-cpp-api > $OUT/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $R/bench.py --full --no-cpu-baseline --no-cpp-api > $OUT/bench_under_rocprof.log 2>&1
 python3 $R/tools/summarize_rocprof.py $(find $OUT/stats -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_summary.csv
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_align -o stats -- python3 $R/tools/exp_align.py 1000000 dof=${3:-5} > $OUT/exp_align.log 2>&1
 python3 $R/tools/summarize_rocprof.py $(find $OUT/stats_align -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_exp_align.csv
@@ -30,7 +30,7 @@ if [ "${2:-}" != "nopmcmix" ]; then
 fi
 MIX=""; [ -s $OUT/pmc_instruction_mix.txt ] && MIX=$OUT/pmc_instruction_mix.txt
 python3 $R/tools/make_k1_traffic.py $OUT/pmc_hbm_traffic.txt $OUT/k1_traffic.json $TAG $MIX > /dev/null 2>&1
-cd $R && python3 bench.py > $OUT/bench.json 2>$OUT/bench.err
+cd $R && python3 bench.py --full > $OUT/bench.json 2>$OUT/bench.err
 tail -1 $OUT/bench_under_rocprof.log | cut -c1-160
 head -12 $OUT/kernel_stats_summary.csv
 head -12 $OUT/kernel_stats_exp_align.csv
