@@ -12,13 +12,12 @@
 #include <type_traits>
 
 #include "ppcr_host_math.hpp"
+#include "ppcr_k1_plan.hpp"  // kNSums, kMaxSplit, the Verlet lists' slot counts
 
 namespace ppcr {
 namespace dev {
 
-constexpr int kNSums = 19;
 constexpr int kBlock = 256;
-constexpr int kMaxSplit = 128;  // K1: blocks that can be scanned as two half-blocks (SplitTable in ppcr_nn_tile.hip.h)
 
 // Uniform grid over the target's bounding box.  Cells are cubes of edge h >= radius in y and z; in x every cell is
 // split into xr slices (edge h / xr, inv_hx = xr * inv_h): a (dy, dz) row of the stencil is one contiguous run
@@ -627,13 +626,6 @@ struct VerletLists {
                           //     sized for the finest level's rows is nothing to the coarsest's; 0 elsewhere)
     int build_all;        // no lists exist yet (or they are not trusted): every workgroup searches and builds
 };
-#ifndef PPCR_VERLET_SLOTS
-#define PPCR_VERLET_SLOTS 16
-#endif
-// list slots per row by the association's compiled-in width M (10 neighbours: 16 slots hold the ~13.5 targets a list's reach
-// holds at the benchmark's density; the command line's 20: 32), and the LDS list slots of the search that builds the lists
-constexpr int verlet_slots(int M) { return M <= 12 ? PPCR_VERLET_SLOTS : 32; }
-constexpr int verlet_scan_slots(int M) { return M <= 12 ? (PPCR_VERLET_SLOTS <= 16 ? 24 : 28) : 36; }
 constexpr int kVerletSlotsMax = 32;
 
 // ---------------------------------------------------------------------------------------------

@@ -282,7 +282,6 @@ struct ppcr_ctx {
     unsigned mbox_seq = 0;             // sequence number of the last fold-and-solve launch (slot = seq % ring)
     DevBuf<Pose> d_pose;               // transform solved by the last reduce_solve_kernel (next K1's move)
     bool move_on_device = false;       // the pending source move is *d_pose (host copy not read back yet)
-    int opt_mailbox = 1;               // 1: deliver the moments through the mailbox and spin (default)
     // device-paced inner loop (ppcr_align with inner_steps > 1): see LoopState / inner_steps_kernel
     DevBuf<LoopState> d_loop;
     DevBuf<unsigned> d_inner_ctl;      // [0..1] step_done (one 64-bit word), [2 ..] completion flags of inner_steps_kernel's K23 workgroups
@@ -326,7 +325,6 @@ struct ppcr_ctx {
     bool have_companion = false, have_ground_truth = false, have_previous = false;
     DevBuf<double> mse_part;
     int opt_short_lists = 1;
-    int opt_k1_halves = 0;       // steady-state K1 scans every block as two half-blocks: 0 never (default), 1 always, -1 small clouds
     int opt_fuse_k23 = 1;        // ppcr_align's one-step iterations fold K23 into the steady-state K1
     int opt_merge_fold = 1;      // ... and the fold-and-solve step rides in the cleanup launch
     bool assoc_folded = false;   // the last association's launches included the fold-and-solve step

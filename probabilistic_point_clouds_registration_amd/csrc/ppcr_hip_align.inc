@@ -122,7 +122,7 @@ struct AlignJob {
         resume_forecasts();
         for (double &v : c->dbg_host) v = 0;
         const bool unbounded = (c->max_nb <= 0 || (int64_t)c->max_nb >= c->nt);
-        pipelined = c->opt_mailbox && c->opt_run_ahead && !unbounded && c->max_nb <= kEllMaxWidth && c->ns > 0;
+        pipelined = c->opt_run_ahead && !unbounded && c->max_nb <= kEllMaxWidth && c->ns > 0;
         max_steps = std::max(inner_steps, 1);
         n_dev_steps = (pipelined && c->nt > 0) ? std::min(max_steps - 1, c->opt_inner_dev_steps) : 0;
         if (pipelined) {
@@ -377,7 +377,7 @@ struct AlignJob {
         return PPCR_OK;
     }
 
-    // host-paced loop (unbounded or very wide searches, options mailbox = 0 / run_ahead = 0): one blocking step at a time
+    // host-paced loop (unbounded or very wide searches, option run_ahead = 0): one blocking step at a time
     int run_host_paced()
     {
         const double nan = std::numeric_limits<double>::quiet_NaN();

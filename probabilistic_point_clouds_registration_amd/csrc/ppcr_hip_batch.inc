@@ -265,7 +265,7 @@ int ppcr_batch_run(const ppcr_pair *pairs, int64_t n_pairs, const ppcr_batch_opt
             std::unique_ptr<Job> job(new AlignJob(make_job(c, opt->n_iter, opt->cost_drop_thresh, opt->n_cost_drop_it, opt->q0, opt->t0,
                                                            opt->inner_steps, opt->f_tol, nullptr, nullptr, nullptr)));
             *rc = job->validate();
-            if (*rc == PPCR_OK && !job->pipelined) *rc = job->run();  // (a handle with the mailbox switched off: here and now)
+            if (*rc == PPCR_OK && !job->pipelined) *rc = job->run();  // (a handle that does not run ahead: here and now)
             if (*rc != PPCR_OK) *err = "pair " + std::to_string(pair_of(k)) + ": " + ppcr_last_error(c);
             return job;
         }

@@ -50,30 +50,16 @@ void launch_accumulate_ell(ppcr_ctx *c, int nb, const Pose &P, const Model &md, 
 
 int flush_pending_move(ppcr_ctx *c);
 
-// the K1 translation unit compiled for the narrowest list width that holds max_neighbours
-void dispatch_tile(TileLaunch &tl, int m)
+// the K1 translation unit compiled for the plan's list width (k1_width: the narrowest that holds max_neighbours)
+void dispatch_tile(TileLaunch &tl)
 {
-    if (m <= 4) launch_tile_m4(tl);
-    else if (m <= 5) launch_tile_m5(tl);
-    else if (m <= 8) launch_tile_m8(tl);
-    else if (m <= 10) launch_tile_m10(tl);
-    else if (m <= 16) launch_tile_m16(tl);
-    else if (m <= 20) launch_tile_m20(tl);
-    else launch_tile_m32(tl);
+    const int M = tl.plan.M;
+    (M == 4 ? launch_tile_m4 : M == 5 ? launch_tile_m5 : M == 8 ? launch_tile_m8 : M == 10 ? launch_tile_m10 : M == 16 ? launch_tile_m16
+     : M == 20 ? launch_tile_m20 : launch_tile_m32)(tl);
 }
 
-// Small clouds leave most of the chip idle with one workgroup per 256 queries (100k points: 391 workgroups on 1280 resident
-// slots) and an iteration lasts as long as ONE workgroup's dependent chain.  Scanning every block as two half-blocks
-// (SplitTable::all_halves; option k1_halves) was built to shorten that chain and MEASURED NEUTRAL TO NEGATIVE: K1 26.3 us
-// with halves against 25.9 us whole at 100k, 23.3 / 22.7 at 50k, 47 / 38 at 250k (docs/experiments.md, round 4) — the
-// chain is the workgroup's dependent memory round trips and LDS latencies, not its scan work.  Off by default.
-bool k1_all_halves(const ppcr_ctx *c)
-{
-    if (c->opt_k1_halves >= 0) return c->opt_k1_halves != 0;
-    return nblocks(std::max<int64_t>(c->ns, 1), 256) <= 640;
-}
 // workgroups of a steady-state K1 launch = slots of the partial sums it leaves when K23 is folded in
-int k1_steady_slots(const ppcr_ctx *c) { return steady_grid(nblocks(std::max<int64_t>(c->ns, 1), 256), k1_all_halves(c)); }
+int k1_steady_slots(const ppcr_ctx *c) { return k1_steady_grid(nblocks(std::max<int64_t>(c->ns, 1), 256)); }
 
 // The largest displacement a rigid move T (row-major [R|t]) gives any point of the target's bounding box — the source lies
 // on the target, and |(R - I) p + t| is convex in p: its maximum over a box sits at a corner.  The Verlet lists are worth
@@ -124,8 +110,8 @@ bool verlet_lists_pay_off(const ppcr_ctx *c)
 // fuse_R / fuse_t (nullable): the pose the first IRLS half-step will be evaluated at; when given, the steady-state K1
 // also produces that step's partial moments (c->assoc_fused, c->fused_slots) and the caller skips the K23 launch.
 struct StepTicket {
-    unsigned seq = 0;  // mailbox sequence number (mailbox path)
-    int nb = 0;        // partial vectors to fold (copy path)
+    unsigned seq = 0;  // mailbox sequence number
+    int nb = 0;        // partial vectors to fold
 };
 int prepare_fold(ppcr_ctx *c, int nslots, StepTicket &tk, FoldSolve &fs, const LoopCtl *loop);
 // merge_tk (with a fuse pose): the fold-and-solve step may ride in the cleanup launch; c->assoc_folded tells whether it did
@@ -179,7 +165,7 @@ int associate_impl(ppcr_ctx *c, const Mat3 *fuse_R = nullptr, const double *fuse
         HIP_TRY(c, c->nbr.reserve((size_t)m * (size_t)std::max(ns, 1)));
         HIP_TRY(c, c->cnt.reserve((size_t)std::max(ns, 1)));
         HIP_TRY(c, c->dm2.reserve((size_t)std::max(ns, 1)));
-        HIP_TRY(c, c->ovf_list.reserve((size_t)std::max(nblocks(std::max(ns, 1), 256) + kMaxSplit, steady_grid(nblocks(std::max(ns, 1), 256), true))));
+        HIP_TRY(c, c->ovf_list.reserve((size_t)k1_max_grid(nblocks(std::max(ns, 1), 256))));
         if (!c->split_clean) {
             const size_t nbk = (size_t)nblocks(std::max(ns, 1), 256);
             HIP_TRY(c, c->split_flag.reserve(nbk));
@@ -220,38 +206,33 @@ int associate_impl(ppcr_ctx *c, const Mat3 *fuse_R = nullptr, const double *fuse
                     fuse = &fm;
                 }
             }
-            bool fused = false, merged = false;
-            // the fold-and-solve step in the same launch as the cleanup: only worth preparing when K23 will be folded
-            // in, i.e. for the steady-state variant (dm2 valid, short lists, m <= 12)
-            FoldSolve fs;
-            const FoldSolve *fold = nullptr;
-            // (also when several handles share the GPU: before the source-order fix of round 3 the merged launch lost there,
-            //  24.0 k it/s against 28.2 k with the small fold kernel for 64 x 250k, 8 in flight; now 41.5 k against 41.0 k,
-            //  and 1.33 k against 0.88 k pairs/s end to end with four pairs in flight)
-            // (m <= 10: the widths that HAVE a steady-state variant are 4, 5, 8 and 10 — launch_tile<M> with M <= 12)
-            const bool steady_next = fuse && c->opt_merge_fold && c->opt_mailbox && c->opt_temporal && c->dm2_valid &&
-                                     c->opt_short_lists && m <= 10 && !c->opt_stamps;
-            if (merge_tk && steady_next) {
-                PPCR_TRY(prepare_fold(c, fm.nslots, *merge_tk, fs, loop));
-                fold = &fs;
-            }
+            // what the plan depends on (ppcr_k1_plan.hpp); the plan itself once the Verlet mode is known
+            K1Query kq{};
+            kq.m = m, kq.blocks = nblocks(std::max(ns, 1), 256);
+            kq.dm2_in = c->opt_temporal && c->dm2_valid, kq.short_lists = c->opt_short_lists != 0, kq.stamps = c->opt_stamps != 0;
+            // (the fold-and-solve step in the same launch as the cleanup — also when several handles share the GPU: before the
+            //  source-order fix of round 3 the merged launch lost there, 24.0 k it/s against 28.2 k with the small fold kernel for
+            //  64 x 250k, 8 in flight; now 41.5 k against 41.0 k, and 1.33 k against 0.88 k pairs/s end to end with four pairs
+            //  in flight)
+            kq.k23_form = fuse_tm, kq.merge_wanted = c->opt_merge_fold && merge_tk != nullptr;
+            kq.reach = c->reach, kq.n_levels = c->n_levels;
+            kq.short_list = k1_wants_short_list(kq);
+            kq.quiet = c->ovf_last == 0, kq.handed_last = c->ovf_last;
             // Verlet lists: the steady-state variant of a one-pass, single-level search builds them (mode 1) and from then on
             // answers from them wherever they still hold (mode 2; the other workgroups search and rebuild)
             // (widths up to 10: K23 can be folded in, 16 list slots; 11 .. 20 — the command line's default is 20 —: the
             //  mid-width variant, 32 slots, rows left to nn_wide_kernel get their lists there; a two-pass search keeps lists
             //  as well: a row's list reaches as far as ITS bound, whichever pass found it)
-            const bool steady_variant = m <= 20 && c->opt_temporal && c->dm2_valid && c->opt_short_lists && !c->opt_stamps;
             // ... once they are predicted to pay off (verlet_lists_pay_off below)
             const bool calm = verlet_lists_pay_off(c);
             // A source far sparser than the target: 256 of its rows span a halo no tile holds, the tiled kernel hands every
             // block over and nn_wide_kernel answers every row (tools/exp_scan_to_map.py).  Once an association has handed
             // (nearly) all blocks over, the next ones do not try: the rows are moved and listed, nothing else (K1 60-90 us ->
             // a few); every 32nd association tries the tiles again.
-            const int n_blocks = nblocks(std::max(ns, 1), 256);
-            const bool list_all = ovf_known != ~0u && n_blocks >= 16 && (double)ovf_known >= 0.9 * (double)n_blocks && (c->assoc_counter++ % 32u) != 31u;
-            const int verlet_mode = (!list_all && steady_variant && c->opt_verlet && c->grid_skin2 > 0 && (c->reach == 1 || m > 10) &&
+            const bool list_all = ovf_known != ~0u && kq.blocks >= 16 && (double)ovf_known >= 0.9 * (double)kq.blocks && (c->assoc_counter++ % 32u) != 31u;
+            const int verlet_mode = (!list_all && k1_has_steady_variant(kq) && c->opt_verlet && c->grid_skin2 > 0 && (c->reach == 1 || m > 10) &&
                                      (c->n_levels <= 1 || c->opt_verlet_levels) &&
-                                     !k1_all_halves(c) && c->nt > 0 && c->ns < (1ll << 26) && (calm || c->opt_verlet == 2))
+                                     c->nt > 0 && c->ns < (1ll << 26) && (calm || c->opt_verlet == 2))
                                         ? ((c->verlet_ok && c->opt_verlet == 1) ? 2 : 1)
                                         : 0;
             if (verlet_mode) {
@@ -262,7 +243,7 @@ int associate_impl(ppcr_ctx *c, const Mat3 *fuse_R = nullptr, const double *fuse
                 HIP_TRY(c, c->vg2.reserve(rows));
                 HIP_TRY(c, c->vacc.reserve(rows));
                 {   // (one byte per workgroup slot of the largest grid a K1 variant launches: two per block, or blocks + split slots)
-                    const size_t slots = (size_t)std::max(steady_grid(nblocks(std::max(ns, 1), 256), true), steady_grid(nblocks(std::max(ns, 1), 256), false));
+                    const size_t slots = (size_t)k1_max_grid(kq.blocks);
                     if (c->vstreak.cap < slots) {
                         HIP_TRY(c, c->vstreak.reserve(slots));
                         HIP_TRY(c, hipMemsetAsync(c->vstreak.p, 0, slots, c->stream));
@@ -276,9 +257,17 @@ int associate_impl(ppcr_ctx *c, const Mat3 *fuse_R = nullptr, const double *fuse
                     c->verlet_order_ok = false;
                 }
             }
+            kq.list_all = list_all, kq.verlet_mode = verlet_mode;
+            kq.verlet_rows = k1_steady_slots(c) <= 1024;  // (one residency round: a searching workgroup is the launch's length)
+            kq.verlet_big_tile = (c->verlet_big_tile || c->opt_verlet_dense == 2) && m <= 10;
+            const K1Plan plan = plan_k1(kq);
+            // the fold-and-solve step rides in the cleanup launch: its buffers, its mailbox sequence number
+            FoldSolve fs;
+            if (plan.merged) PPCR_TRY(prepare_fold(c, fm.nslots, *merge_tk, fs, loop));
             ProfScope ps(c, K_NN_TOPM);
             c->ovf_parity ^= 1;
             TileLaunch tl{};
+            tl.plan = plan;
             tl.stream = c->stream;
             tl.src = c->src.p, tl.ns = (int)c->ns, tl.tgt = c->tgt_sorted.p, tl.cell_start = c->cell_start.p, tl.grid = c->grid;
             tl.r2 = r2, tl.m = m;
@@ -298,13 +287,8 @@ int associate_impl(ppcr_ctx *c, const Mat3 *fuse_R = nullptr, const double *fuse
                 for (int l = 0; l < kMaxLevels; l++) tl.r2_cap[l] = c->level_r2_cap[l];
                 tl.level_dbg = (c->opt_level_stats && c->level_dbg.p) ? c->level_dbg.p : nullptr;
             }
-            // who redoes the rows of handed-over workgroups: the cleanup role of the second launch when K23 is folded in (it
-            // folds K23 for them as well, but walks a dense neighbourhood one candidate per lane at a time), nn_wide_kernel
-            // otherwise — every launch that cannot fold, every two-pass search (an idle nn_wide_kernel costs what an idle
-            // cleanup launch costs, and the choice does not depend on when a hand-over count reaches the host)
-            // (K23 can only be folded in by the steady-state variant: widths up to 10, a valid cut-off, short lists)
-            const bool may_fuse = fuse != nullptr && m <= 10 && c->opt_temporal && c->dm2_valid && c->opt_short_lists && !c->opt_stamps;
-            if (c->reach > 1 || c->n_levels > 1 || !may_fuse) {
+            // the rows of handed-over workgroups (and the short rows of a two-pass search) are listed for nn_wide_kernel
+            if (plan.wide) {
                 if (c->d_short.cap < (size_t)ns + 3) {
                     HIP_TRY(c, hipStreamSynchronize(c->stream));
                     HIP_TRY(c, c->d_short.reserve((size_t)ns + 3));
@@ -316,15 +300,12 @@ int associate_impl(ppcr_ctx *c, const Mat3 *fuse_R = nullptr, const double *fuse
             }
             if (c->d_short.p) tl.short_next = reinterpret_cast<unsigned *>(c->d_short.p) + (c->ovf_parity ^ 1);
             tl.nbr = c->nbr.p, tl.cnt = c->cnt.p, tl.dm2 = c->dm2.p;
-            tl.dm2_in = (c->opt_temporal && c->dm2_valid) ? 1 : 0;
-            tl.short_lists = c->opt_short_lists;
-            tl.list_all = (list_all && tl.short_count != nullptr) ? 1 : 0;
-            tl.all_halves = k1_all_halves(c) ? 1 : 0;
+            tl.dm2_in = kq.dm2_in ? 1 : 0;
             if (c->opt_stamps) {
-                // sized from the grid this launch really has (the steady-state variant adds kMaxSplit workgroups in front):
+                // sized from the grid this launch really has (the steady-state variant adds kMaxSplit workgroups in front, a
+                // multi-level search launches two per block; the reader sums the records of exactly this grid):
                 // 8 words per wave, then one word per lane (its sorted run lengths)
-                // (a multi-level search launches two workgroups per block; the reader sums the records of exactly this grid)
-                const size_t nwg = c->n_levels > 1 ? (size_t)steady_grid(nblocks(ns, 256), true) : (size_t)std::max(nblocks(ns, 256) + kMaxSplit, k1_steady_slots(c));
+                const size_t nwg = (size_t)plan.grid;
                 const size_t nst = (nwg * (kBlock / 64) + 64) * 8 + nwg * 256;
                 if (c->d_stamps.cap < nst) {
                     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -336,15 +317,10 @@ int associate_impl(ppcr_ctx *c, const Mat3 *fuse_R = nullptr, const double *fuse
             tl.stamps = c->opt_stamps ? c->d_stamps.p : nullptr;
             tl.ovf_list = c->ovf_list.p;
             tl.ovf_now = c->ovf_state.p + c->ovf_parity, tl.ovf_next = c->ovf_state.p + (c->ovf_parity ^ 1);
-            tl.quiet = c->ovf_last == 0;
-            tl.handed_last = c->ovf_last;
             tl.split_flag = c->split_flag.p, tl.split_list = c->split_list.p, tl.split_state = c->split_state.p;
-            tl.pm = pm, tl.fuse = fuse, tl.fold = fold;
-            tl.fuse_tm = fuse_tm;
+            tl.pm = pm, tl.fuse = fuse, tl.fold = plan.merged ? &fs : nullptr;
             tl.loop_st = loop ? loop->st : nullptr;
             tl.verlet_mode = verlet_mode;
-            tl.verlet_rows = k1_steady_slots(c) <= 1024 ? 1 : 0;  // (one residency round: a searching workgroup is the launch's length)
-            tl.verlet_big_tile = ((c->verlet_big_tile || c->opt_verlet_dense == 2) && m <= 10) ? 1 : 0;
             if (verlet_mode) {
                 tl.verlet.vl = c->vl.p, tl.verlet.vn = c->vn.p, tl.verlet.vg2 = c->vg2.p, tl.verlet.vacc = c->vacc.p;
                 tl.verlet.vmask = c->vmask.p;
@@ -381,20 +357,14 @@ int associate_impl(ppcr_ctx *c, const Mat3 *fuse_R = nullptr, const double *fuse
             tl.between2 = [](void *scope) { static_cast<ProfScope *>(scope)->split(K_NN_WIDE); };
             tl.between_arg = &ps;
             trace_mark(c, "reserved");
-            dispatch_tile(tl, m);
+            dispatch_tile(tl);
             trace_mark(c, "k1");
-            fused = tl.fused, merged = tl.merged;
-            c->verlet_ok = tl.verlet_built;
-            if (tl.verlet_built) c->verlet_launches++;
-            c->verlet_order_ok = tl.verlet_built;
-            c->assoc_fused = fused;
-            c->assoc_folded = merged;
-            c->fused_slots = fused ? fm.nslots : 0;
-            if (fold && !merged) {
-                // (cannot happen while steady_next mirrors launch_tile's dispatch; were it to, the sequence number
-                //  drawn for the fold is handed back and the caller launches the fold on its own)
-                c->mbox_seq--;
-            }
+            c->verlet_ok = plan.verlet_built;
+            if (plan.verlet_built) c->verlet_launches++;
+            c->verlet_order_ok = plan.verlet_built;
+            c->assoc_fused = plan.fused;
+            c->assoc_folded = plan.merged;
+            c->fused_slots = plan.fused ? fm.nslots : 0;
         }
         c->assoc_space = 1;
         PPCR_TRY(check_launch(c, "nn_fast_kernel"));
@@ -657,27 +627,20 @@ int launch_step(ppcr_ctx *c, const Mat3 &R, const double t[3], StepTicket &tk, b
     }
     PPCR_TRY(check_launch(c, "accumulate_kernel"));
     tk.nb = nb;
-    if (c->opt_mailbox) {
-        // fold + solve on the device; moments, transform and cost arrive in the host mailbox ring
-        FoldSolve fs;
-        PPCR_TRY(prepare_fold(c, nb, tk, fs, loop));
-        const auto tl0 = std::chrono::steady_clock::now();
-        {
-            ProfScope ps(c, K_REDUCE);
-            reduce_solve_kernel<<<kNSums, kBlock, 0, c->stream>>>(fs);
-        }
-        PPCR_TRY(check_launch(c, "reduce_solve_kernel"));
-        c->dbg_host[6] = std::max(c->dbg_host[6], std::chrono::duration<double>(std::chrono::steady_clock::now() - tl0).count());
-        return PPCR_OK;
-    }
+    // fold + solve on the device; moments, transform and cost arrive in the host mailbox ring
+    FoldSolve fs;
+    PPCR_TRY(prepare_fold(c, nb, tk, fs, loop));
+    const auto tl0 = std::chrono::steady_clock::now();
     {
         ProfScope ps(c, K_REDUCE);
-        reduce_partials_kernel<<<kNSums, kBlock, 0, c->stream>>>(c->partials.p, nb, c->d_sums.p);
+        reduce_solve_kernel<<<kNSums, kBlock, 0, c->stream>>>(fs);
     }
-    return check_launch(c, "reduce_partials_kernel");
+    PPCR_TRY(check_launch(c, "reduce_solve_kernel"));
+    c->dbg_host[6] = std::max(c->dbg_host[6], std::chrono::duration<double>(std::chrono::steady_clock::now() - tl0).count());
+    return PPCR_OK;
 }
 
-// has that step's result reached the host mailbox yet?  (mailbox path only; never blocks)
+// has that step's result reached the host mailbox yet?  (never blocks)
 bool step_arrived(const ppcr_ctx *c, const StepTicket &tk)
 {
     const HostMailbox *mb = c->h_mbox + (tk.seq % kMailboxRing);
@@ -687,54 +650,43 @@ bool step_arrived(const ppcr_ctx *c, const StepTicket &tk)
 // wait for that step and fetch its result
 int collect_step(ppcr_ctx *c, const StepTicket &tk, StepResult &out)
 {
-    if (c->opt_mailbox) {
-        const HostMailbox *mb = c->h_mbox + (tk.seq % kMailboxRing);
-        volatile const unsigned *flag = &mb->seq;
-        bool arrived = false;
-        const auto tw0 = std::chrono::steady_clock::now();
-        for (long spin = 0; spin < 200000000L; spin++) {  // ~ seconds; a fault on the device ends up below
-            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == tk.seq) {
-                arrived = true;
-                break;
-            }
-            // a short wait is spun through (an iteration lasts ~0.1 ms); past that the core is offered to whoever
-            // else wants it, so many handles driven from more threads than cores do not starve each other
-            if (spin > 4096) std::this_thread::yield();
-            // (a device fault must not take seconds to surface: look at the stream every 2^16 polls, a few milliseconds)
-            if ((spin & 0xFFFF) == 0xFFFF && hipStreamQuery(c->stream) != hipErrorNotReady) {
-                arrived = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == tk.seq;
-                break;
-            }
+    const HostMailbox *mb = c->h_mbox + (tk.seq % kMailboxRing);
+    volatile const unsigned *flag = &mb->seq;
+    bool arrived = false;
+    const auto tw0 = std::chrono::steady_clock::now();
+    for (long spin = 0; spin < 200000000L; spin++) {  // ~ seconds; a fault on the device ends up below
+        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == tk.seq) {
+            arrived = true;
+            break;
         }
-        if (!arrived) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != tk.seq) return fail(c, PPCR_ERR_HIP, "moment mailbox never arrived");
+        // a short wait is spun through (an iteration lasts ~0.1 ms); past that the core is offered to whoever
+        // else wants it, so many handles driven from more threads than cores do not starve each other
+        if (spin > 4096) std::this_thread::yield();
+        // (a device fault must not take seconds to surface: look at the stream every 2^16 polls, a few milliseconds)
+        if ((spin & 0xFFFF) == 0xFFFF && hipStreamQuery(c->stream) != hipErrorNotReady) {
+            arrived = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == tk.seq;
+            break;
         }
-        for (int j = 0; j < kNSums; j++) out.sums[j] = mb->sums[j];
-        for (int j = 0; j < 12; j++) out.T[j] = mb->T[j];
-        out.cost = mb->cost;
-        out.degenerate = mb->degenerate != 0;
-        out.status = mb->status;
-        out.steps = mb->steps;
-        out.cost_init = mb->cost_init;
-        if (out.status != kLaunchSkipped) {
-            c->ovf_last = mb->handed_over;
-            c->dbg_host[7] += (double)mb->handed_over;  // workgroups the associations of this ppcr_align handed to the cleanup kernel
-        }
-        const double w = std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count();
-        c->dbg_host[0] += 1;
-        c->dbg_host[1] += w;
-        c->dbg_host[2] = std::max(c->dbg_host[2], w);
-        return PPCR_OK;
     }
-    // copy path: moments back, solve on the host (same source as the device solve)
-    HIP_TRY(c, hipMemcpyAsync(c->h_sums, c->d_sums.p, sizeof(double) * kNSums, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    std::memcpy(out.sums, c->h_sums, sizeof(double) * kNSums);
-    const RigidSolve rs = solve_rigid_from_moments(out.sums, c->origin);
-    pack_T(rs.R, rs.t, out.T);
-    out.degenerate = rs.degenerate;
-    out.cost = rs.degenerate ? 0.5 * out.sums[16] : cost_from_moments(out.sums, c->origin, rs.R, rs.t);
+    if (!arrived) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != tk.seq) return fail(c, PPCR_ERR_HIP, "moment mailbox never arrived");
+    }
+    for (int j = 0; j < kNSums; j++) out.sums[j] = mb->sums[j];
+    for (int j = 0; j < 12; j++) out.T[j] = mb->T[j];
+    out.cost = mb->cost;
+    out.degenerate = mb->degenerate != 0;
+    out.status = mb->status;
+    out.steps = mb->steps;
+    out.cost_init = mb->cost_init;
+    if (out.status != kLaunchSkipped) {
+        c->ovf_last = mb->handed_over;
+        c->dbg_host[7] += (double)mb->handed_over;  // workgroups the associations of this ppcr_align handed to the cleanup kernel
+    }
+    const double w = std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count();
+    c->dbg_host[0] += 1;
+    c->dbg_host[1] += w;
+    c->dbg_host[2] = std::max(c->dbg_host[2], w);
     return PPCR_OK;
 }
 

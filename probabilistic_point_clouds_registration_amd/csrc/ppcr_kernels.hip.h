@@ -778,35 +778,6 @@ __global__ __launch_bounds__(kBlock, ONEPASS ? PPCR_INNER_PER_CU : 3) void inner
     if (threadIdx.x == 0) __hip_atomic_store(&ic->flags[(size_t)u * G + r], seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// fold partials[19][nblocks] -> sums[19].  One 256-thread block PER SUM (grid = 19): every thread issues its
-// (up to 8 per trip) loads of a contiguous row back to back, so the fold costs about one memory round trip;
-// then a wave shuffle tree and a fixed-order LDS combine: deterministic summation order, no atomics.
-__global__ __launch_bounds__(kBlock) void reduce_partials_kernel(const double *__restrict__ partials, int nblocks,
-                                                                 double *__restrict__ sums)
-{
-    __shared__ double sh[kBlock / 64];
-    const double *row = partials + (size_t)blockIdx.x * nblocks;
-    double v = 0.0;
-    for (int b0 = 0; b0 < nblocks; b0 += 8 * kBlock) {
-        double t[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int b = b0 + u * kBlock + threadIdx.x;
-            t[u] = (b < nblocks) ? row[b] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 8; u++) v += t[u];
-    }
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double x = sh[0];
-        for (int w = 1; w < kBlock / 64; w++) x += sh[w];
-        sums[blockIdx.x] = x;
-    }
-}
-
 // ProbabilisticWeights::updateWeights on caller-supplied squared errors (probabilistic_weights.hpp:48-105):
 // one lane per CSR row, the reference's exact formula (lp, row max, mll, exp(lp - mll) [* (v+d)/(v+s)]).
 __global__ void weights_from_errors_kernel(const int *__restrict__ row_ptr, int64_t n_rows,

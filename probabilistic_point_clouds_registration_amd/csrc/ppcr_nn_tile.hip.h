@@ -2148,7 +2148,7 @@ __global__ __launch_bounds__(256, (VERLET_K != 0 ? (CAP * 13 + C * 512 > 40960 ?
         // unanswered rows are listed, nn_wide_kernel searches them (marked unsearched)
         if (tid == 0) ovf_list[atomicAdd(ovf_count, 1u)] = (int)wg * 4 + half;
         if constexpr (VERLET) {
-            if (valid) vv.vg2[i] = 0.f;  // (whoever redoes these rows builds no lists: they come back here next time)
+            if (valid) vv.vg2[i] = 0.f;  // (nn_wide_kernel gives these rows fresh lists where it redoes them; the cleanup role builds none: they come back here next time)
             if (tid == 0) verlet_file_slot(vv, wg, true);
         }
         if constexpr (MULTI) {

@@ -2,24 +2,12 @@
 // (ppcr_nn_tile.hip, compiled once per list width M): everything one K1 launch needs, by value.
 #pragma once
 #include "ppcr_device.hip.h"
+#include "ppcr_k1_plan.hpp"
 
 namespace ppcr {
 
-// Halo capacity of the steady-state (16-slot) variant: 31.3 KB of LDS, five workgroups per CU (1792: four).
-constexpr int kCapSteady = 1728;
-// ... of the Verlet variant (four workgroups per CU either way: its list path holds 48 coordinates in registers), whose
-// lists reach further than the plain search's cut-off: larger cells, larger halos
-constexpr int kCapVerlet = 1920;
-// ... and of that variant where the cloud is denser (a block's halo outgrows 1920 candidates for more blocks than can be split):
-// the first association's 2240-candidate tile, three workgroups per CU (TileLaunch::verlet_big_tile)
-constexpr int kCapVerletBig = 2240;
-// ... and of the Verlet variant of the mid-width lists (the command line's 20 neighbours: 32-slot Verlet lists, 36-slot scan
-// lists — 18.9 KB — beside the halo: 1600 candidates keep the kernel at four workgroups per CU)
-constexpr int kCapVerletMid = 1600;
-// workgroups (= partial-sum slots when K23 is folded in) of a steady-state K1 launch over nb blocks of 256 queries
-inline int steady_grid(int nb, bool all_halves) { return all_halves ? 2 * ((nb + 7) & ~7) : nb + dev::kMaxSplit; }
-
 struct TileLaunch {
+    K1Plan plan;                  // which kernels run, on what grids (plan_k1: the caller sizes its buffers from the same plan)
     hipStream_t stream;
     float4 *src;                  // the (sorted) source; moved in place when pm.enabled
     int ns;
@@ -44,14 +32,9 @@ struct TileLaunch {
     int *nbr, *cnt;               // the ELL association [m][ns], [ns]
     unsigned *dm2;                // per query: float bits of its m-th neighbour's d2 (the temporal cut-off)
     int dm2_in;                   // dm2 of the previous association is usable
-    int short_lists;              // option short_lists
-    int list_all;                 // with short_count: try no tile, list every row (UnansweredRows::list_all)
-    int all_halves;               // steady-state variant: scan every block as two half-blocks (small clouds; see SplitTable)
     unsigned long long *stamps;   // diagnostic build only (nullptr otherwise)
     int *ovf_list;                // workgroups handed to the cleanup kernel by this launch ...
     unsigned *ovf_now, *ovf_next; // ... counted here; the other counter of the ping-pong pair
-    bool quiet;                   // the last association this handle heard from handed nothing over
-    unsigned handed_last;         // ... how many workgroups it handed over (~0u: not known)
     unsigned char *split_flag;    // the split table (see SplitTable)
     int *split_list;
     unsigned *split_state;        // {registrations, registrations visible to extra workgroups}
@@ -59,18 +42,12 @@ struct TileLaunch {
     dev::VerletLists verlet;        // steady-state Verlet lists (buffers of [16][ns] + per-row state), used when verlet_mode != 0:
     int verlet_mode;                //   0 off; 1 this association builds every row's list; 2 workgroups whose rows' lists still
                                     //   hold answer from them, the others search and rebuild
-    int verlet_rows;                //   widths up to 10: the kernel variant that rebuilds a few failing rows inside the workgroup
-    int verlet_big_tile;            //   widths up to 10: the 2240-candidate tile (three workgroups per CU) — denser clouds
-    const dev::FusedMoments *fuse;  // fold K23 into K1 at this pose / model when the steady-state variant runs
-    int fuse_tm;                    // ... in this compiled form: 0 Gaussian, 8 t with v + dim = 8, -3 t with another integer v + dim
-    const dev::FoldSolve *fold;     // ... and the fold-and-solve step into the cleanup launch
+    const dev::FusedMoments *fuse;  // the pose / model of the K23 the plan folds into K1 (plan.fused)
+    const dev::FoldSolve *fold;     // ... and the fold-and-solve step that rides in the cleanup launch (plan.merged)
     dev::LoopState *loop_st;        // device-paced loop: every launch steps aside while its abort flag is up (nullable)
     void (*between)(void *);        // called between the two launches (profiling scopes), may be null
     void (*between2)(void *);       // ... and before the second pass of a two-pass search
     void *between_arg;
-    // out
-    bool fused, merged;
-    bool verlet_built;              // the launch wrote / kept Verlet lists (the steady-state variant ran in Verlet mode)
 };
 
 // One entry per compiled-in list width (register list of the selection); defined in ppcr_nn_tile.hip.
