@@ -301,6 +301,49 @@ int ppcr_voxel_filter(int device_id, const float *xyz, int64_t n, int64_t stride
 int ppcr_nearest_sq_distances(int device_id, const float *queries, int64_t nq, int64_t q_stride_bytes,
                               const float *targets, int64_t nt, int64_t t_stride_bytes, float *d2_out);
 
+/* ---- many candidate poses of one source scored against one resident target ----------------------------------------
+ * The closest-point metrics of utilities.hpp:28-234 as the fitness function of a global (swarm) search: the target, its
+ * grid and the source stay on the device; one call scores n_poses rigid poses T_p = [R|t] (3 x 4, row-major) and returns
+ * five numbers per pose.  Nothing crosses the host between the search, the selection of the medians and the sums.
+ *
+ * d_i (pose p, i < n = nq) is the float squared distance from float(T_p x_i) to its exact nearest target: the move is the
+ * f64-math, f32-store arithmetic of ppcr_apply_transform, the distance the un-fused float d^2 of the association, so d_i
+ * is bit for bit what ppcr_nearest_sq_distances returns for the moved cloud.  The source itself is never modified.
+ *
+ * With d sorted ascending (0-based) the reference's "median" is  M(d) = d[(n+1)/2]  for odd n and
+ * (double(d[n/2]) + double(d[n/2+1])) / 2.0  for even n (its off-by-one included); it reads out of bounds for n < 3,
+ * where the value here is NaN.  The band of a pose is  median/factor <= v <= median*factor, evaluated in double.
+ *
+ * The six metrics of the reference from one ppcr_pose_score s:
+ *   averageClosestDistance          s.sum / n
+ *   sumSquaredError                 s.sum
+ *   robustSumSquaredError           s.robust_count < 10 ? DBL_MAX : s.robust_sum
+ *   robustAveragedSumSquaredError   s.robust_sum / s.robust_count
+ *   medianClosestDistance           s.median
+ *   robustMedianClosestDistance     s.robust_median / s.robust_count
+ * Two calls with the same inputs return the same bits. */
+typedef struct ppcr_scorer ppcr_scorer;
+typedef struct ppcr_pose_score {
+    double sum;           /* sum of d_i */
+    double median;        /* M(d); NaN when n < 3 */
+    double robust_sum;    /* sum of the d_i inside the band */
+    int64_t robust_count; /* how many d_i are inside the band */
+    double robust_median; /* M(the in-band d_i), NOT divided by the count; NaN when robust_count < 3 */
+} ppcr_pose_score;
+/* uploads the target and builds its grid, once; nt must be > 0 */
+int ppcr_scorer_create(int device_id, const float *target, int64_t nt, int64_t stride_bytes, ppcr_scorer **out);
+int ppcr_scorer_set_source(ppcr_scorer *s, const float *xyz, int64_t nq, int64_t stride_bytes);
+/* T: n_poses x 12; factor >= 1 and finite; scores: n_poses; d2_out: NULL, or n_poses x nq floats (query order).
+ * PPCR_ERR_STATE before a source is set.  n_poses == 0 and nq == 0 are valid (nq == 0: sums and count 0, medians NaN).
+ * Poses are processed in chunks that bound the d^2 scratch; the call synchronises once, at its end. */
+int ppcr_scorer_score(ppcr_scorer *s, const double *T, int64_t n_poses, double factor, ppcr_pose_score *scores,
+                      float *d2_out);
+/* device time (HIP events) of the search launches of the last ppcr_scorer_score call, in milliseconds */
+int ppcr_scorer_last_search_ms(ppcr_scorer *s, double *ms);
+/* message of the last failing call on this scorer (NULL: of the last failing ppcr_scorer_create on this thread) */
+const char *ppcr_scorer_last_error(const ppcr_scorer *s);
+int ppcr_scorer_destroy(ppcr_scorer *s);
+
 int ppcr_synchronize(ppcr_ctx *ctx);
 
 /* Per-kernel device timing with HIP events recorded on the handle's own stream. */

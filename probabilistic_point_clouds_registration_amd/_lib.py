@@ -25,6 +25,8 @@ SYMBOLS = [
     "ppcr_get_companion", "ppcr_set_ground_truth", "ppcr_mse_ground_truth", "ppcr_mse_previous", "ppcr_voxel_filter",
     "ppcr_nearest_sq_distances", "ppcr_stop_rule_check", "ppcr_align_report", "ppcr_batch_release",
     "ppcr_memory_stats", "ppcr_memory_trim",
+    "ppcr_scorer_create", "ppcr_scorer_set_source", "ppcr_scorer_score", "ppcr_scorer_last_search_ms",
+    "ppcr_scorer_last_error", "ppcr_scorer_destroy",
     "ppcr_comm_get_id", "ppcr_comm_create", "ppcr_comm_destroy", "ppcr_gather_transforms", "ppcr_comm_last_error",
 ]
 
@@ -133,9 +135,16 @@ def load():
     L.ppcr_comm_destroy.argtypes = [vp]
     L.ppcr_gather_transforms.argtypes = [vp, vp, i64, vp]
     L.ppcr_comm_last_error.restype = C.c_char_p
+    L.ppcr_scorer_create.argtypes = [i32, vp, i64, i64, C.POINTER(vp)]
+    L.ppcr_scorer_set_source.argtypes = [vp, vp, i64, i64]
+    L.ppcr_scorer_score.argtypes = [vp, vp, i64, dbl, vp, vp]
+    L.ppcr_scorer_last_search_ms.argtypes = [vp, C.POINTER(dbl)]
+    L.ppcr_scorer_last_error.argtypes = [vp]
+    L.ppcr_scorer_last_error.restype = C.c_char_p
+    L.ppcr_scorer_destroy.argtypes = [vp]
     for name in SYMBOLS:
         f = getattr(L, name)
-        if name not in ("ppcr_last_error", "ppcr_cost_from_moments", "ppcr_comm_last_error"):
+        if name not in ("ppcr_last_error", "ppcr_cost_from_moments", "ppcr_comm_last_error", "ppcr_scorer_last_error"):
             f.restype = i32
     _lib = L
     return L
@@ -602,3 +611,73 @@ def nearest_sq_distances(queries, targets, device_id=0):
     if rc != 0:
         raise PpcrError(rc, L.ppcr_last_error(None).decode())
     return out[:q.shape[0]].copy()
+
+
+class PoseScore(C.Structure):
+    """ppcr_pose_score"""
+    _fields_ = [("sum", C.c_double), ("median", C.c_double), ("robust_sum", C.c_double), ("robust_count", C.c_int64),
+                ("robust_median", C.c_double)]
+
+
+class Scorer:
+    """ppcr_scorer: one target (and its grid) and one source resident on the device; score() takes many poses at once."""
+
+    def __init__(self, target, device_id=0):
+        self._L = load()
+        t = _cloud(target)
+        h = C.c_void_p()
+        rc = self._L.ppcr_scorer_create(int(device_id), t.ctypes.data if t.size else None, t.shape[0], t.shape[1] * 4, C.byref(h))
+        if rc != 0:
+            raise PpcrError(rc, self._L.ppcr_scorer_last_error(None).decode())
+        self._h = h
+        self.nq = 0
+
+    def _ck(self, rc):
+        if rc != 0:
+            raise PpcrError(rc, self._L.ppcr_scorer_last_error(self._h).decode())
+
+    def set_source(self, q):
+        q = _cloud(q)
+        self._ck(self._L.ppcr_scorer_set_source(self._h, q.ctypes.data if q.size else None, q.shape[0], q.shape[1] * 4))
+        self.nq = q.shape[0]
+
+    def score(self, T, factor=3.0, want_d2=False):
+        """T: [P, 3, 4] (or [P, 4, 4], or one such matrix) -> dict of arrays of length P: sum, median, robust_sum,
+        robust_count, robust_median (ppcr.h: ppcr_pose_score) and, with want_d2, d2 float32 [P, nq]."""
+        T = np.asarray(T, dtype=np.float64)
+        if T.ndim == 2:
+            T = T[None]
+        T = np.ascontiguousarray(T[:, :3, :4]).reshape(-1, 12)
+        P = T.shape[0]
+        scores = (PoseScore * max(P, 1))()
+        d2 = np.zeros((P, self.nq), dtype=np.float32) if want_d2 else None
+        self._ck(self._L.ppcr_scorer_score(self._h, T.ctypes.data if P else None, P, float(factor), scores,
+                                           d2.ctypes.data if want_d2 and d2.size else None))
+        out = {name: np.array([getattr(scores[p], name) for p in range(P)], dtype=np.int64 if name == "robust_count" else np.float64)
+               for name, _ in PoseScore._fields_}
+        if want_d2:
+            out["d2"] = d2
+        return out
+
+    def last_search_ms(self):
+        ms = C.c_double(0)
+        self._ck(self._L.ppcr_scorer_last_search_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.ppcr_scorer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

@@ -31,6 +31,7 @@
 #include "ppcr_batch_sched.hpp"
 #include "ppcr_kernels.hip.h"
 #include "ppcr_nn_tile_launch.hip.h"
+#include "ppcr_score.hip.h"
 
 using namespace ppcr;
 using namespace ppcr::dev;
@@ -371,3 +372,4 @@ void trace_print(ppcr_ctx *c)
 #include "ppcr_hip_align.inc"      // the registration loop (AlignJob) and ppcr_align / ppcr_align_report
 #include "ppcr_hip_extras.inc"     // companion cloud, reports, VoxelGrid, 1-NN distances
 #include "ppcr_hip_batch.inc"      // ppcr_align_many, ppcr_batch_run
+#include "ppcr_hip_score.inc"      // ppcr_scorer: many candidate poses scored against a resident target
