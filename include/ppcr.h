@@ -309,6 +309,11 @@ int ppcr_nearest_sq_distances(int device_id, const float *queries, int64_t nq, i
  * d_i (pose p, i < n = nq) is the float squared distance from float(T_p x_i) to its exact nearest target: the move is the
  * f64-math, f32-store arithmetic of ppcr_apply_transform, the distance the un-fused float d^2 of the association, so d_i
  * is bit for bit what ppcr_nearest_sq_distances returns for the moved cloud.  The source itself is never modified.
+ * Subnormal d_i are kept (nothing here flushes denormals): they are ordered, selected, compared with the band and summed
+ * like any other value.  A source row with a NaN or an infinite coordinate has d_i = +inf under every pose (no distance
+ * compares below +inf); it still counts towards n, makes sum +inf and, when such rows reach the middle ranks, the
+ * medians and the band edges +inf (the band is then exactly the +inf values).  A target row with a NaN coordinate is never
+ * the nearest of any query and does not enter the grid's box.
  *
  * With d sorted ascending (0-based) the reference's "median" is  M(d) = d[(n+1)/2]  for odd n and
  * (double(d[n/2]) + double(d[n/2+1])) / 2.0  for even n (its off-by-one included); it reads out of bounds for n < 3,

@@ -47,12 +47,30 @@ def _median(v):
     return v[(m + 1) // 2] if m % 2 else (v[m // 2] + v[m // 2 + 1]) / 2.0
 
 
-def _reference(q, t, T):
+def _reference(q, t, T, factor=FACTOR):
     d2 = po.nearest_sq_distances(po.transform_cloud(q.copy(), T), t)
     v = np.sort(d2).astype(np.float64)
     med = _median(v)
-    band = v[(v <= med * FACTOR) & (v >= med / FACTOR)]
+    band = v[(v <= med * factor) & (v >= med / factor)]
     return d2, dict(sum=v.sum(), median=med, robust_sum=band.sum(), robust_count=len(band), robust_median=_median(band))
+
+
+KEYS = ("sum", "median", "robust_sum", "robust_count", "robust_median")
+
+
+def _assert_pose(got, p, d2, ref, n, tag):
+    """pose p of a call against its reference: d2 and the order statistics bit for bit, the sums within 2 n u |ref| (all terms
+    are >= 0: any summation order is within n u of the true sum); a sum that is not finite must be equal (|inf - inf| is NaN)"""
+    print(tag, p, {k: (got[k][p], ref[k]) for k in ref})
+    if "d2" in got:
+        np.testing.assert_array_equal(got["d2"][p], d2, err_msg=f"{tag} pose {p} d2")
+    for k in ("median", "robust_median", "robust_count"):
+        np.testing.assert_array_equal(got[k][p], ref[k], err_msg=f"{tag} pose {p} {k}")
+    for k in ("sum", "robust_sum"):
+        if np.isfinite(ref[k]):
+            assert abs(got[k][p] - ref[k]) <= 2 * n * 2.0 ** -53 * abs(ref[k]), (tag, p, k, got[k][p], ref[k])
+        else:
+            np.testing.assert_array_equal(got[k][p], ref[k], err_msg=f"{tag} pose {p} {k}")
 
 
 @pytest.mark.parametrize("case", list(CLOUDS))
@@ -101,3 +119,273 @@ def test_error_returns_and_empty_inputs():
         np.testing.assert_array_equal(got["robust_sum"], [0, 0])
         np.testing.assert_array_equal(got["robust_count"], [0, 0])
         assert np.isnan(got["median"]).all() and np.isnan(got["robust_median"]).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# 1. Crafted d2 multisets.  With a target at the origin the d2 of a query is x*x + y*y + z*z, exact in float for short dyadic
+# coordinates, so the sorted d2 of a source is known by construction: which digit of the radix select (11 / 11 / 10 bits of
+# the float pattern) separates the two middle elements, what the band keeps, how many values lie below it.
+# ---------------------------------------------------------------------------------------------------------------------------
+_E = 2.0 ** -70                     # coordinates whose squares are subnormal floats
+_S = 2.0 ** -140
+_NAN, _INF = float("nan"), float("inf")
+_XYZ = {   # d2 -> a point at exactly that squared distance from the origin ("nan", "+inf", ...: a row whose d2 is +inf)
+    0: (0, 0, 0), 2.0 ** -6: (0.125, 0, 0), 0.25: (0, 0.5, 0), 1: (1, 0, 0), 1 + 2.0 ** -20: (1, 2.0 ** -10, 0),
+    1 + 2.0 ** -10: (1, 0, 2.0 ** -5), 1.125: (1, 0.25, 0.25), 2: (1, 1, 0), 2.25: (0, 1.5, 0), 4: (0, 2, 0), 8: (2, 0, 2),
+    16: (0, 0, 4), 64: (8, 0, 0), "s1": (_E, 0, 0), "s4": (0, 2 * _E, 0), "s9": (0, 0, 3 * _E),
+    "nan": (_NAN, 0, 0), "+inf": (0, _INF, 0), "-inf": (1, 1, -_INF), "nan3": (_NAN, _NAN, _NAN)}
+_SMALL3 = {2.0 ** -6: 3}            # three values far below any band around 1
+
+# name -> ({d2: how many}, factor, what the case is there for: asserted on the reference before the device is looked at)
+CRAFTED = {
+    # even n, sorted[n/2] and sorted[n/2+1] apart in the first, only the second, only the third digit
+    "median_digit1": ({1: 5, 4: 3}, 2.0,
+                      dict(mid_digit=1, median=2.5, below=5, robust_count=3, robust_sum=12, robust_median=4)),
+    "median_digit2": ({1: 5, 1 + 2.0 ** -10: 3}, 3.0, dict(mid_digit=2, median=1 + 2.0 ** -11, below=0, robust_count=8)),
+    "median_digit3": ({1: 5, 1 + 2.0 ** -20: 3}, 3.0, dict(mid_digit=3, median=1 + 2.0 ** -21, below=0, robust_count=8)),
+    # the same for the band's middles, the band starting above the smallest values
+    "robust_digit1": ({**_SMALL3, 1: 4, 2: 2}, 3.0,
+                      dict(median=1, below=3, robust_count=6, rmid_digit=1, robust_sum=8, robust_median=1.5)),
+    "robust_digit2": ({**_SMALL3, 1: 4, 1 + 2.0 ** -10: 2}, 3.0,
+                      dict(median=1, below=3, robust_count=6, rmid_digit=2, robust_median=1 + 2.0 ** -11)),
+    "robust_digit3": ({**_SMALL3, 1: 4, 1 + 2.0 ** -20: 2}, 3.0,
+                      dict(median=1, below=3, robust_count=6, rmid_digit=3, robust_median=1 + 2.0 ** -21)),
+    # the band's edges are inclusive, in double
+    "edges_inclusive": ({0.25: 2, 1: 5, 4: 2}, 4.0, dict(median=1, below=0, robust_count=9, robust_sum=13.5, robust_median=1)),
+    "edges_just_missed": ({0.25: 2, 1: 5, 4: 2}, float(np.nextafter(4.0, 0.0)),
+                          dict(median=1, below=2, robust_count=5, robust_sum=5, robust_median=1)),
+    "factor1_empty_band": ({1: 3, 4: 1}, 1.0,
+                           dict(mid_digit=1, median=2.5, below=3, robust_count=0, robust_sum=0, robust_median=_NAN)),
+    "factor1_all_equal": ({1: 5}, 1.0, dict(median=1, below=0, robust_count=5, robust_sum=5, robust_median=1)),
+    # robust_count 1 .. 4 (0: factor1_empty_band); the robust median is NaN below 3
+    "count1": ({**_SMALL3, 1: 1, 64: 1}, 3.0, dict(median=1, below=3, robust_count=1, robust_median=_NAN)),
+    "count2": ({2.0 ** -6: 2, 1: 2, 64: 1}, 3.0, dict(median=1, below=2, robust_count=2, robust_median=_NAN)),
+    "count3": ({2.0 ** -6: 1, 1: 1, 1.125: 1, 2: 1, 64: 1}, 3.0, dict(median=2, below=1, robust_count=3, robust_median=2)),
+    "count4": ({2.0 ** -6: 1, 1: 1, 1.125: 1, 2: 1, 2.25: 1, 64: 1}, 3.0,
+               dict(median=2.125, below=1, robust_count=4, rmid_digit=2, robust_median=2.125)),
+    "n3": ({1: 1, 2: 1, 4: 1}, 3.0, dict(median=4, below=1, robust_count=2, robust_median=_NAN)),
+    "n4": ({1: 1, 2: 1, 4: 1, 8: 1}, 3.0, dict(median=6, below=1, robust_count=3, robust_sum=14, robust_median=8)),
+    "n5": ({1: 1, 2: 1, 4: 1, 8: 1, 16: 1}, 3.0, dict(median=8, below=2, robust_count=3, robust_sum=28, robust_median=16)),
+    # more than half of the queries sit on the target
+    "median_zero_even": ({0: 6, 1: 1, 4: 1}, 3.0, dict(median=0, below=0, robust_count=6, robust_sum=0, robust_median=0)),
+    "median_zero_odd": ({0: 5, 1: 1, 4: 1}, 3.0, dict(median=0, below=0, robust_count=5, robust_sum=0, robust_median=0)),
+    # subnormal d2 are kept, not flushed
+    "subnormal_odd": ({0: 1, "s1": 2, "s4": 2, "s9": 1, 1: 2, 4: 1}, 3.0,
+                      dict(subnormal=True, median=9 * _S, below=3, robust_count=3, robust_sum=17 * _S, robust_median=9 * _S)),
+    "subnormal_even": ({"s1": 4, "s4": 1, "s9": 1, 1: 1, 4: 1}, 3.0,
+                       dict(subnormal=True, mid_digit=2, median=6.5 * _S, below=4, robust_count=2, robust_median=_NAN)),
+    # d2 = +inf (a query row with a NaN or an infinite coordinate), the target carrying a row with a NaN as well
+    "inf_minority": ({1: 2, 2: 2, 4: 2, "nan": 1, "+inf": 1, "-inf": 1}, 3.0,
+                     dict(nan_target=True, sum=_INF, median=4, below=2, robust_count=4, robust_sum=12, robust_median=4)),
+    "inf_majority_odd": ({1: 1, 2: 1, 4: 2, "nan": 2, "+inf": 1, "-inf": 1, "nan3": 1}, 3.0,
+                         dict(nan_target=True, sum=_INF, median=_INF, below=4, robust_count=5, robust_sum=_INF,
+                              robust_median=_INF)),
+    "inf_majority_even": ({1: 1, 2: 1, 4: 1, "nan": 2, "+inf": 2, "-inf": 1}, 3.0,
+                          dict(nan_target=True, sum=_INF, median=_INF, below=3, robust_count=5, robust_sum=_INF,
+                               robust_median=_INF)),
+    "inf_upper_middle": ({1: 1, 2: 1, 4: 2, 8: 1, "nan": 1, "+inf": 1, "-inf": 1}, 3.0,
+                         dict(nan_target=True, mid_digit=1, sum=_INF, median=_INF, below=5, robust_count=3, robust_sum=_INF,
+                              robust_median=_INF)),
+}
+EYE = np.hstack([np.eye(3), np.zeros((3, 1))])
+QUARTER_Z = np.array([[0.0, -1, 0, 0], [1, 0, 0, 0], [0, 0, 1, 0]])   # entries 0 and +-1: the moved coordinates keep their bits
+FAR_TARGETS = np.array([[384, 256, 128], [256, 384, 64]], np.float32)
+
+
+def _digit(a, b):
+    """the digit of the select (11 / 11 / 10 bits from the top) at which two floats part; 0: the same pattern"""
+    a, b = (int(np.array(x, np.float32).view(np.uint32)) for x in (a, b))
+    return 1 if a >> 21 != b >> 21 else 2 if a >> 10 != b >> 10 else 3 if a != b else 0
+
+
+def _crafted_source(counts):
+    q = np.array([_XYZ[v] for v, k in counts.items() for _ in range(k)], np.float32)
+    return q[np.random.default_rng(len(q)).permutation(len(q))]
+
+
+def _assert_structure(case, q, d2, ref, factor, want):
+    """the case is what its name says: d2 is the exact x*x + y*y + z*z (+inf for a non-finite row) and the sorted multiset has
+    the wanted middles, band and count below the band"""
+    q64 = q.astype(np.float64)
+    exact = np.where(np.isfinite(q64).all(1), (q64 * q64).sum(1), np.inf)
+    np.testing.assert_array_equal(exact.astype(np.float32).astype(np.float64), exact, err_msg=f"{case}: d2 not a float")
+    np.testing.assert_array_equal(d2, exact.astype(np.float32), err_msg=f"{case}: the oracle's d2")
+    s = np.sort(d2)
+    v = s.astype(np.float64)
+    n = len(s)
+    in_band = (v <= ref["median"] * factor) & (v >= ref["median"] / factor)
+    band = s[in_band]
+    for k, x in want.items():
+        if k == "mid_digit":
+            assert n % 2 == 0 and _digit(s[n // 2], s[n // 2 + 1]) == x, (case, k, s.view(np.uint32))
+        elif k == "rmid_digit":
+            m = len(band)
+            assert m % 2 == 0 and m >= 4 and _digit(band[m // 2], band[m // 2 + 1]) == x, (case, k, band.view(np.uint32))
+        elif k == "below":
+            assert int((v < ref["median"] / factor).sum()) == x, (case, k)
+        elif k == "subnormal":
+            assert 0 < ref["median"] < 2.0 ** -126, (case, k)
+        elif k != "nan_target":
+            np.testing.assert_array_equal(ref[k], x, err_msg=f"{case}: reference {k}")
+
+
+@pytest.mark.parametrize("targets", ["origin", "corner"])
+@pytest.mark.parametrize("case", list(CRAFTED))
+def test_crafted_multisets(case, targets):
+    counts, factor, want = CRAFTED[case]
+    q = _crafted_source(counts)
+    t = np.zeros((1, 3), np.float32)
+    if targets == "corner":                             # a grid of several cells, the queries in one corner of it
+        t = np.vstack([t, FAR_TARGETS])
+    if want.get("nan_target"):
+        t = np.vstack([t, np.array([[_NAN, 1, 1]], np.float32)])
+    T = np.stack([EYE, QUARTER_Z])
+    with _lib.Scorer(t) as sc:
+        sc.set_source(q)
+        got = sc.score(T, factor=factor, want_d2=True)
+    for p in range(len(T)):
+        d2, ref = _reference(q, t, T[p], factor)
+        _assert_structure(case, q, d2, ref, factor, want)
+        _assert_pose(got, p, d2, ref, len(q), f"{case}/{targets}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# 2. Block and span boundaries of the source: 256 queries per search block, 4096 per block of the streaming passes, and the
+# partials of more than 256 blocks folded by one workgroup of 256 lanes (257 search blocks: 65 537; 257 stream blocks: 1 048 577).
+# ---------------------------------------------------------------------------------------------------------------------------
+SMALL_TARGET = (np.random.default_rng(21).random((300, 3)) * [30, 20, 10]).astype(np.float32)   # brute force stays cheap
+_cache = {}
+
+
+def _random_source(nq):
+    if ("random", nq) not in _cache:
+        _cache["random", nq] = (np.random.default_rng(nq).random((nq, 3)) * [36, 26, 16] - 3).astype(np.float32)
+    return _cache["random", nq]
+
+
+def _tiled_source(nq):
+    """a jittered tiling of the target's box: nearly every query lies in the target and ends in the private scan"""
+    if ("tiled", nq) not in _cache:
+        k = int(np.ceil(nq ** (1 / 3)))
+        i = np.arange(nq)
+        cell = np.stack([i % k, (i // k) % k, i // (k * k)], axis=1)
+        _cache["tiled", nq] = ((cell + np.random.default_rng(nq).random((nq, 3))) / k * [30, 20, 10]).astype(np.float32)
+    return _cache["tiled", nq]
+
+
+def _seven_poses(q):
+    """_poses' identity, small move, 2 rad turn and 400 units away, and three more: seven distinct poses"""
+    c = q.astype(np.float64).mean(0)
+    back = np.hstack([synth.rodrigues(np.array([-0.6, 0.1, 0.3]), -0.05), [[-0.3], [0.2], [0.1]]])
+    quarter = np.hstack([QUARTER_Z[:, :3], (c - QUARTER_Z[:, :3] @ c)[:, None]])
+    shift = np.hstack([np.eye(3), [[1.5], [-2.0], [0.5]]])
+    return np.concatenate([_poses(q)[:4], np.stack([back, quarter, shift])])
+
+
+def _reference_of(kind, nq, p):
+    """the reference of pose p of _seven_poses over a cached source: computed once, shared, never written to"""
+    if (kind, nq, p) not in _cache:
+        q = (_tiled_source if kind == "tiled" else _random_source)(nq)
+        _cache[kind, nq, p] = _reference(q, SMALL_TARGET, _seven_poses(q)[p])
+    return _cache[kind, nq, p]
+
+
+@pytest.mark.parametrize("nq", [255, 256, 257, 4095, 4096, 4097, 65537])
+def test_block_and_span_edges(nq):
+    q, t = _random_source(nq), SMALL_TARGET
+    T = _seven_poses(q)[:3]
+    src = q
+    if nq == 4097:                                      # stride 16 (pcl::PointXYZ), the fourth float anything at all
+        pad = np.resize(np.array([_NAN, 1e30, -7.0, _INF], np.float32), nq)
+        src = np.hstack([q, pad[:, None]])
+    with _lib.Scorer(t) as sc:
+        sc.set_source(src)
+        got = sc.score(T, factor=FACTOR, want_d2=True)
+    for p in range(len(T)):
+        d2, ref = _reference_of("random", nq, p)
+        _assert_pose(got, p, d2, ref, nq, f"nq={nq}")
+    if nq == 4097:                                      # ppcr.h: d2 is what ppcr_nearest_sq_distances gives for the moved cloud
+        moved = po.transform_cloud(q.copy(), T[2])
+        np.testing.assert_array_equal(got["d2"][2], _lib.nearest_sq_distances(moved, t))
+
+
+@pytest.mark.parametrize("nq", [1048577, 1048578])
+def test_more_stream_blocks_than_lanes(nq):
+    q, t = _tiled_source(nq), SMALL_TARGET
+    T = _seven_poses(q)[:3]
+    with _lib.Scorer(t) as sc:
+        sc.set_source(q)
+        got = sc.score(T, factor=FACTOR, want_d2=True)
+    for p in range(len(T)):
+        d2, ref = _reference_of("tiled", nq, p)
+        _assert_pose(got, p, d2, ref, nq, f"nq={nq}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# 3. Pose chunks.  What a pose scores must not depend on where in the call it stands: seven distinct poses (coprime to the
+# four poses of a search workgroup: every pose meets every slot) tiled to the call's length, the first occurrence of each
+# against the oracle, every later one against the first, bit for bit.
+# ---------------------------------------------------------------------------------------------------------------------------
+def _assert_tiled_call(got, kind, nq, tag):
+    P = len(got["sum"])
+    first = np.arange(P) % 7
+    for p in range(min(P, 7)):
+        d2, ref = _reference_of(kind, nq, p)
+        _assert_pose(got, p, d2, ref, nq, tag)
+    for k in KEYS:
+        a = got[k].view(np.int64)
+        np.testing.assert_array_equal(a, a[first], err_msg=f"{tag} {k}")
+    if "d2" in got:
+        a = got["d2"].view(np.uint32)
+        for j in range(7, P):
+            assert np.array_equal(a[j], a[j - 7]), (tag, "d2 of pose", j)
+
+
+def test_chunks_by_pose_count():
+    nq, P = 300, 2 * 4096 + 3                           # three chunks, the last of 3 poses
+    q = _random_source(nq)
+    T = _seven_poses(q)[np.arange(P) % 7]
+    with _lib.Scorer(SMALL_TARGET) as sc:
+        sc.set_source(q)
+        got = sc.score(T, factor=FACTOR, want_d2=True)
+        ms = sc.last_search_ms()
+        assert np.isfinite(ms) and ms > 0, ms           # summed over the chunks' event pairs
+        sc.score(np.zeros((0, 3, 4)))
+        assert sc.last_search_ms() == 0
+    _assert_tiled_call(got, "random", nq, "8195 poses")
+
+
+def test_chunks_by_d2_bytes():
+    nq = 1048577
+    # ppcr_scorer_score: a chunk holds min(4096, PPCR_SCORE_D2_BYTES / (4 nq)) poses, PPCR_SCORE_D2_BYTES = 256 MiB
+    cap = min(4096, (256 << 20) // (4 * nq))
+    P = cap + 5
+    assert 4 < cap < P
+    q = _tiled_source(nq)
+    seven = _seven_poses(q)
+    with _lib.Scorer(SMALL_TARGET) as sc:
+        sc.set_source(q)
+        got = sc.score(seven[np.arange(P) % 7], factor=FACTOR)
+        _assert_tiled_call(got, "tiled", nq, f"{P} poses")
+        got = sc.score(seven[np.arange(cap + 1) % 7], factor=FACTOR, want_d2=True)   # the d2 rows of the second chunk
+        _assert_tiled_call(got, "tiled", nq, f"{cap + 1} poses, d2")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# 4. One scorer, many calls: the scratch only grows and is cut anew per call (poses per chunk, blocks per pose), so every
+# call must give the bits a fresh scorer gives for it.
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_one_scorer_many_calls():
+    a, b, empty = _random_source(70001), _random_source(5), np.zeros((0, 3), np.float32)
+    nine = np.concatenate([_seven_poses(a), _seven_poses(a)[1:3]])
+    calls = [(a, nine), (b, _seven_poses(b)[1:2]), (a, nine[2:5]), (empty, nine[:2]), (a, nine)]
+    with _lib.Scorer(SMALL_TARGET) as used:
+        for k, (q, T) in enumerate(calls):
+            used.set_source(q)
+            got = used.score(T, factor=FACTOR, want_d2=True)
+            with _lib.Scorer(SMALL_TARGET) as fresh:
+                fresh.set_source(q)
+                ref = fresh.score(T, factor=FACTOR, want_d2=True)
+            for key in KEYS:
+                np.testing.assert_array_equal(got[key].view(np.int64), ref[key].view(np.int64), err_msg=f"call {k} {key}")
+            np.testing.assert_array_equal(got["d2"].view(np.uint32), ref["d2"].view(np.uint32), err_msg=f"call {k} d2")
