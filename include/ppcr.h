@@ -349,6 +349,46 @@ int ppcr_scorer_last_search_ms(ppcr_scorer *s, double *ms);
 const char *ppcr_scorer_last_error(const ppcr_scorer *s);
 int ppcr_scorer_destroy(ppcr_scorer *s);
 
+/* ---- many candidate poses of the scorer's source refined with the registration's own objective ----------------------
+ * The second step of a global search: the best few dozen poses are polished by n_iter registration iterations each, all
+ * poses in the same launches (two per iteration), the association never leaving the chip and the host not asked anything
+ * until the end of the call.
+ *
+ * One iteration for a pose T does what a handle does in the sequence ppcr_set_source(float(T x_i)) — the move is the
+ * arithmetic of ppcr_apply_transform, bit for bit — ppcr_associate with (radius, max_neighbours), ppcr_iterate with
+ * inner_steps = 1 from the identity: a pair is kept when its float d^2 is strictly below (float)(radius * radius); a row
+ * keeps its max_neighbours closest pairs in (d^2, original target index) order; the weights and the 19 moments are f64,
+ * about the centre of the target's box; the solve is closed-form.  The pose then becomes T_step * T, composed in f64, and
+ * the next iteration starts from it.  The source itself is never modified.
+ *
+ * Not ppcr_align: ppcr_align moves the f32 cloud in place every iteration, so its roundings to f32 accumulate in the
+ * cloud; here every iteration moves the ORIGINAL cloud by the accumulated f64 pose — for a pose that is being searched
+ * over, the better definition.  The two agree to the f32 rounding of the coordinates, not to the bit.
+ * There is no stopping rule, only n_iter, and no inner loop beyond the one IRLS step per iteration.
+ *
+ * A pose whose association has no pair (weight_sum not > 0) is frozen: it keeps its T, reports cost = {0, 0},
+ * weight_sum = 0 and n_pairs = 0, and stays put for the remaining iterations.
+ * Every f64 sum is folded in a fixed order and the counts are integers: the same inputs give the same bits, and a pose's
+ * result depends neither on the other poses of the call nor on its place among them. */
+typedef struct ppcr_pose_step {
+    double T[12];        /* the pose after this iteration's step: T_step * T_in, composed in f64 */
+    double cost[2];      /* initial_cost, final_cost of the step (Ceres' 1/2 factor), as ppcr_iterate reports them */
+    double weight_sum;   /* moment [0]: sum of the weights of the association this step was solved on */
+    int64_t n_pairs;     /* nnz of that association */
+} ppcr_pose_step;
+/* the search of ppcr_scorer_refine.  Supported: radius positive and finite, 0 < max_neighbours <= 20 (no unbounded
+ * search), dof > 0 (INFINITY: Gaussian weights), dim > 0; anything else PPCR_ERR_INVALID.  A new radius has the target's
+ * radius grid rebuilt (from the device copy) at the next ppcr_scorer_refine. */
+int ppcr_scorer_set_params(ppcr_scorer *s, double radius, int max_neighbours, double dof, int dim);
+/* T: n_poses x 12; last: n_poses records, the state after the n_iter-th iteration; history: NULL, or n_iter x n_poses
+ * records, iteration-major.  PPCR_ERR_STATE before a source or the parameters are set; PPCR_ERR_INVALID for n_iter < 0.
+ * n_poses == 0 and n_iter == 0 are valid: with n_iter == 0, last[p].T = T_p and the other fields are zero.  The call
+ * enqueues everything and synchronises once, at its end. */
+int ppcr_scorer_refine(ppcr_scorer *s, const double *T, int64_t n_poses, int n_iter, ppcr_pose_step *last,
+                       ppcr_pose_step *history);
+/* device time (HIP events) around the whole train of launches of the last ppcr_scorer_refine call, in milliseconds */
+int ppcr_scorer_last_refine_ms(ppcr_scorer *s, double *ms);
+
 int ppcr_synchronize(ppcr_ctx *ctx);
 
 /* Per-kernel device timing with HIP events recorded on the handle's own stream. */

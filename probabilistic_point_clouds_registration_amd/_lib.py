@@ -27,6 +27,7 @@ SYMBOLS = [
     "ppcr_memory_stats", "ppcr_memory_trim",
     "ppcr_scorer_create", "ppcr_scorer_set_source", "ppcr_scorer_score", "ppcr_scorer_last_search_ms",
     "ppcr_scorer_last_error", "ppcr_scorer_destroy",
+    "ppcr_scorer_set_params", "ppcr_scorer_refine", "ppcr_scorer_last_refine_ms",
     "ppcr_comm_get_id", "ppcr_comm_create", "ppcr_comm_destroy", "ppcr_gather_transforms", "ppcr_comm_last_error",
 ]
 
@@ -142,6 +143,9 @@ def load():
     L.ppcr_scorer_last_error.argtypes = [vp]
     L.ppcr_scorer_last_error.restype = C.c_char_p
     L.ppcr_scorer_destroy.argtypes = [vp]
+    L.ppcr_scorer_set_params.argtypes = [vp, dbl, i32, dbl, i32]
+    L.ppcr_scorer_refine.argtypes = [vp, vp, i64, i32, vp, vp]
+    L.ppcr_scorer_last_refine_ms.argtypes = [vp, C.POINTER(dbl)]
     for name in SYMBOLS:
         f = getattr(L, name)
         if name not in ("ppcr_last_error", "ppcr_cost_from_moments", "ppcr_comm_last_error", "ppcr_scorer_last_error"):
@@ -662,6 +666,39 @@ class Scorer:
     def last_search_ms(self):
         ms = C.c_double(0)
         self._ck(self._L.ppcr_scorer_last_search_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def set_params(self, radius, max_neighbours, dof, dim=3):
+        """The search and the weight model of refine(): 0 < max_neighbours <= 20."""
+        self._ck(self._L.ppcr_scorer_set_params(self._h, float(radius), int(max_neighbours), float(dof), int(dim)))
+
+    def refine(self, T, n_iter=1, want_history=False):
+        """n_iter registration iterations (search, weights, one closed-form step) of every pose of T ([P, 3, 4], [P, 4, 4] or
+        one matrix) in the same launches -> dict: T [P, 3, 4], cost [P, 2], weight_sum [P], n_pairs [P] after the last
+        iteration (ppcr.h: ppcr_pose_step) and, with want_history, "history": the same with a leading iteration axis."""
+        T = np.asarray(T, dtype=np.float64)
+        if T.ndim == 2:
+            T = T[None]
+        T = np.ascontiguousarray(T[:, :3, :4]).reshape(-1, 12)
+        P = T.shape[0]
+        last = np.zeros((max(P, 1), 16))   # ppcr_pose_step: 15 doubles and one int64
+        hist = np.zeros((max(int(n_iter), 0), max(P, 1), 16)) if want_history else None
+        self._ck(self._L.ppcr_scorer_refine(self._h, T.ctypes.data if P else None, P, int(n_iter), last.ctypes.data,
+                                            hist.ctypes.data if want_history and hist.size else None))
+
+        def unpack(a):
+            a = a[..., :P, :]
+            return dict(T=a[..., :12].reshape(a.shape[:-1] + (3, 4)).copy(), cost=a[..., 12:14].copy(),
+                        weight_sum=a[..., 14].copy(), n_pairs=np.ascontiguousarray(a[..., 15]).view(np.int64))
+
+        out = unpack(last)
+        if want_history:
+            out["history"] = unpack(hist)
+        return out
+
+    def last_refine_ms(self):
+        ms = C.c_double(0)
+        self._ck(self._L.ppcr_scorer_last_refine_ms(self._h, C.byref(ms)))
         return ms.value
 
     def close(self):

@@ -26,7 +26,9 @@ DEPS = SOURCES + [os.path.join(CSRC, h) for h in ("ppcr_device.hip.h", "ppcr_ker
                                                   "ppcr_hip_setup.inc", "ppcr_hip_iteration.inc", "ppcr_hip_api.inc",
                                                   "ppcr_hip_align.inc", "ppcr_hip_extras.inc", "ppcr_hip_batch.inc",
                                                   # the pose scorer: its kernels and its host side
-                                                  "ppcr_score.hip.h", "ppcr_hip_score.inc")] + [
+                                                  "ppcr_score.hip.h", "ppcr_hip_score.inc",
+                                                  # the pose refinement on the same scorer
+                                                  "ppcr_refine.hip.h", "ppcr_hip_refine.inc")] + [
     os.path.join(ROOT, "include", "ppcr.h")]
 
 

@@ -32,6 +32,7 @@
 #include "ppcr_kernels.hip.h"
 #include "ppcr_nn_tile_launch.hip.h"
 #include "ppcr_score.hip.h"
+#include "ppcr_refine.hip.h"
 
 using namespace ppcr;
 using namespace ppcr::dev;
@@ -373,3 +374,4 @@ void trace_print(ppcr_ctx *c)
 #include "ppcr_hip_extras.inc"     // companion cloud, reports, VoxelGrid, 1-NN distances
 #include "ppcr_hip_batch.inc"      // ppcr_align_many, ppcr_batch_run
 #include "ppcr_hip_score.inc"      // ppcr_scorer: many candidate poses scored against a resident target
+#include "ppcr_hip_refine.inc"     // ppcr_scorer_refine: many candidate poses polished by fused search, weights and solve

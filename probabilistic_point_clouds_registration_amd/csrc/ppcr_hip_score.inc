@@ -18,6 +18,19 @@ struct ppcr_scorer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> search_events;  // one pair per chunk of the last call
     size_t search_events_used = 0;
     double last_search_ms = 0;
+    // ppcr_scorer_refine (ppcr_hip_refine.inc): its parameters, the target sorted by cells of edge >= radius, the source in
+    // brick order of its own box, and the scratch of a call
+    bool r_have_params = false, r_src_valid = false;
+    double r_radius = 0, r_dof = 0, r_grid_radius = -1;
+    int r_max_nb = 0, r_dim = 3;
+    GridDesc r_grid{};
+    DevBuf<float4> r_tgt, r_src;
+    DevBuf<int> r_cell_start;
+    DevBuf<double> r_partials, r_poses;  // r_partials: [pose][kRefineSums][blocks]
+    DevBuf<unsigned> r_frozen;
+    DevBuf<ppcr_pose_step> r_steps;
+    hipEvent_t r_ev[2] = {nullptr, nullptr};
+    double last_refine_ms = 0;
 };
 
 namespace {
@@ -134,6 +147,7 @@ int ppcr_scorer_set_source(ppcr_scorer *s, const float *xyz, int64_t nq, int64_t
 {
     if (!s) return PPCR_ERR_INVALID;
     CTX_ENTER(s->c);
+    s->r_src_valid = false;  // (the refinement's sorted copy is made again at its next call)
     return set_source_common(s->c, xyz, false, nq, stride_bytes);
 }
 
@@ -210,6 +224,15 @@ int ppcr_scorer_destroy(ppcr_scorer *s)
     s->d_sel.release_idle();
     s->d_rcount.release_idle();
     s->d_scores.release_idle();
+    for (hipEvent_t ev : s->r_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    s->r_tgt.release_idle();
+    s->r_src.release_idle();
+    s->r_cell_start.release_idle();
+    s->r_partials.release_idle();
+    s->r_poses.release_idle();
+    s->r_frozen.release_idle();
+    s->r_steps.release_idle();
     ppcr_destroy(s->c);
     delete s;
     return PPCR_OK;
