@@ -389,6 +389,29 @@ int ppcr_scorer_refine(ppcr_scorer *s, const double *T, int64_t n_poses, int n_i
 /* device time (HIP events) around the whole train of launches of the last ppcr_scorer_refine call, in milliseconds */
 int ppcr_scorer_last_refine_ms(ppcr_scorer *s, double *ms);
 
+/* ---- unbounded radius search without an association ----
+ * max_neighbours <= 0 means "every target inside the radius".  With no cut there is nothing to select, so these calls
+ * never build the list of pairs: one kernel streams the cell-sorted target past every source row, decides membership
+ * (float d^2 < (float)(radius * radius) on the unmoved point, as every search here) and folds the weights and moments
+ * at the pose on the fly.  No memory per pair, and no 32-bit limit on the number of pairs.
+ *
+ * moments of the implicit unbounded association of the CURRENT source at pose (q,t): what
+ * ppcr_set_params(max_neighbours = 0) + ppcr_associate + ppcr_accumulate(q,t) return, to rounding;
+ * n_pairs (nullable) = that association's nnz, exact, 64-bit.  Uses radius, dof, dim of ppcr_set_params and
+ * ignores max_neighbours.  Neither needs nor creates nor disturbs a stored association.
+ * PPCR_ERR_STATE without target, source or parameters; an empty cloud gives zero moments and n_pairs = 0. */
+int ppcr_accumulate_radius(ppcr_ctx *ctx, const double q[4], const double t[3], double sums[PPCR_NSUMS], int64_t *n_pairs);
+
+/* ppcr_iterate on that implicit association: IRLS from (q0,t0) (kernel -> fold -> device solve per step, the stopping
+ * test of ppcr_solve), then the source moved by the increment.  n_pairs nullable. */
+int ppcr_iterate_radius(ppcr_ctx *ctx, const double q0[4], const double t0[3], int inner_steps, double f_tol,
+                        double T_out[12], double cost_out[2], int *steps_out, int64_t *n_pairs);
+
+/* the ppcr_align loop (ppcr_stop_rule_check, history / costs / steps / n_done as there) over ppcr_iterate_radius */
+int ppcr_align_radius(ppcr_ctx *ctx, int n_iter, double cost_drop_thresh, double n_cost_drop_it, const double q0[4],
+                      const double t0[3], int inner_steps, double f_tol, double *history, double *costs,
+                      int32_t *steps, int *n_done);
+
 int ppcr_synchronize(ppcr_ctx *ctx);
 
 /* Per-kernel device timing with HIP events recorded on the handle's own stream. */

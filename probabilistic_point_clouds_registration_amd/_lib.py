@@ -28,6 +28,7 @@ SYMBOLS = [
     "ppcr_scorer_create", "ppcr_scorer_set_source", "ppcr_scorer_score", "ppcr_scorer_last_search_ms",
     "ppcr_scorer_last_error", "ppcr_scorer_destroy",
     "ppcr_scorer_set_params", "ppcr_scorer_refine", "ppcr_scorer_last_refine_ms",
+    "ppcr_accumulate_radius", "ppcr_iterate_radius", "ppcr_align_radius",
     "ppcr_comm_get_id", "ppcr_comm_create", "ppcr_comm_destroy", "ppcr_gather_transforms", "ppcr_comm_last_error",
 ]
 
@@ -146,6 +147,9 @@ def load():
     L.ppcr_scorer_set_params.argtypes = [vp, dbl, i32, dbl, i32]
     L.ppcr_scorer_refine.argtypes = [vp, vp, i64, i32, vp, vp]
     L.ppcr_scorer_last_refine_ms.argtypes = [vp, C.POINTER(dbl)]
+    L.ppcr_accumulate_radius.argtypes = [vp, vp, vp, vp, C.POINTER(i64)]
+    L.ppcr_iterate_radius.argtypes = [vp, vp, vp, i32, dbl, vp, vp, C.POINTER(i32), C.POINTER(i64)]
+    L.ppcr_align_radius.argtypes = [vp, i32, dbl, dbl, vp, vp, i32, dbl, vp, vp, vp, C.POINTER(i32)]
     for name in SYMBOLS:
         f = getattr(L, name)
         if name not in ("ppcr_last_error", "ppcr_cost_from_moments", "ppcr_comm_last_error", "ppcr_scorer_last_error"):
@@ -294,8 +298,30 @@ class Context:
                                       T.ctypes.data, cost.ctypes.data, C.byref(st)))
         return T.reshape(3, 4), cost, st.value
 
+    def accumulate_radius(self, q, t):
+        """Moments and exact pair count of the unbounded radius search (every target inside the radius) at the pose,
+        without an association being stored."""
+        sums, n = np.zeros(NSUMS), C.c_int64(0)
+        q, t = _f64(q, 4), _f64(t, 3)
+        self._ck(self._L.ppcr_accumulate_radius(self._h, q.ctypes.data, t.ctypes.data, sums.ctypes.data, C.byref(n)))
+        return sums, n.value
+
+    def iterate_radius(self, q0=(1, 0, 0, 0), t0=(0, 0, 0), inner_steps=1, f_tol=1e-5):
+        """iterate() on that implicit association; also returns its pair count."""
+        T, cost, st, n = np.zeros(12), np.zeros(2), C.c_int(0), C.c_int64(0)
+        q0, t0 = _f64(q0, 4), _f64(t0, 3)
+        self._ck(self._L.ppcr_iterate_radius(self._h, q0.ctypes.data, t0.ctypes.data, int(inner_steps), float(f_tol),
+                                             T.ctypes.data, cost.ctypes.data, C.byref(st), C.byref(n)))
+        return T.reshape(3, 4), cost, st.value, n.value
+
+    def align_radius(self, n_iter, cost_drop_thresh=0.0, n_cost_drop_it=5, q0=(1, 0, 0, 0), t0=(0, 0, 0),
+                     inner_steps=1, f_tol=1e-5, want_history=True):
+        """align() over iterate_radius: same arguments, same result dictionary."""
+        return self.align(n_iter, cost_drop_thresh, n_cost_drop_it, q0, t0, inner_steps, f_tol, want_history,
+                          _entry=self._L.ppcr_align_radius)
+
     def align(self, n_iter, cost_drop_thresh=0.0, n_cost_drop_it=5, q0=(1, 0, 0, 0), t0=(0, 0, 0),
-              inner_steps=1, f_tol=1e-5, want_history=True):
+              inner_steps=1, f_tol=1e-5, want_history=True, _entry=None):
         """n_iter < 0 = no iteration cap (the reference's meaning): only with want_history=False and
         cost_drop_thresh > 0 — the per-iteration arrays could not be sized and the loop would never end."""
         if int(n_iter) < 0 and want_history:
@@ -306,7 +332,7 @@ class Context:
         steps = np.zeros(k, dtype=np.int32) if want_history else None
         done = C.c_int(0)
         q0, t0 = _f64(q0, 4), _f64(t0, 3)
-        self._ck(self._L.ppcr_align(self._h, int(n_iter), float(cost_drop_thresh), float(n_cost_drop_it),
+        self._ck((_entry or self._L.ppcr_align)(self._h, int(n_iter), float(cost_drop_thresh), float(n_cost_drop_it),
                                     q0.ctypes.data, t0.ctypes.data, int(inner_steps), float(f_tol),
                                     hist.ctypes.data if want_history else None,
                                     costs.ctypes.data if want_history else None,

@@ -18,7 +18,8 @@ MAIN_TU = os.path.join(CSRC, "ppcr_hip.hip")
 COMM_TU = os.path.join(CSRC, "ppcr_comm.hip")   # the native RCCL gather (host code only; RCCL bound at run time)
 TILE_TU = os.path.join(CSRC, "ppcr_nn_tile.hip")
 TILE_WIDTHS = (10, 4, 5, 8, 16, 20, 32)   # K1's compiled-in list widths, one object each (the default first)
-SOURCES = [MAIN_TU, TILE_TU, COMM_TU]
+RADIUS_TU = os.path.join(CSRC, "ppcr_radius.hip")   # radius_moments_kernel, a unit of its own (see _jobs)
+SOURCES = [MAIN_TU, TILE_TU, COMM_TU, RADIUS_TU]
 DEPS = SOURCES + [os.path.join(CSRC, h) for h in ("ppcr_device.hip.h", "ppcr_kernels.hip.h", "ppcr_nn_tile.hip.h",
                                                   "ppcr_nn_tile_launch.hip.h", "ppcr_k1_plan.hpp", "ppcr_host_math.hpp", "ppcr_pool.hpp",
                                                   "ppcr_batch_sched.hpp",
@@ -28,7 +29,9 @@ DEPS = SOURCES + [os.path.join(CSRC, h) for h in ("ppcr_device.hip.h", "ppcr_ker
                                                   # the pose scorer: its kernels and its host side
                                                   "ppcr_score.hip.h", "ppcr_hip_score.inc",
                                                   # the pose refinement on the same scorer
-                                                  "ppcr_refine.hip.h", "ppcr_hip_refine.inc")] + [
+                                                  "ppcr_refine.hip.h", "ppcr_hip_refine.inc",
+                                                  # unbounded radius iterations without an association
+                                                  "ppcr_radius.hip.h", "ppcr_hip_radius.inc")] + [
     os.path.join(ROOT, "include", "ppcr.h")]
 
 
@@ -55,7 +58,12 @@ def needs_build():
 def _jobs():
     """(object, compile command) for every translation unit: the C-ABI unit and K1 once per list width."""
     cc = [hipcc()] + flags() + ["-c"]
-    jobs = [(os.path.join(OBJ, "ppcr_hip.o"), cc + [MAIN_TU]), (os.path.join(OBJ, "ppcr_comm.o"), cc + [COMM_TU])]
+    # radius_moments_kernel without packed f32 arithmetic: left to itself the compiler pairs the x and y terms of its
+    # membership distance into v_pk_add_f32 / v_pk_mul_f32; the scalar forms round the same way.  Every other unit is
+    # built as before.
+    no_pk = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+    jobs = [(os.path.join(OBJ, "ppcr_hip.o"), cc + [MAIN_TU]), (os.path.join(OBJ, "ppcr_comm.o"), cc + [COMM_TU]),
+            (os.path.join(OBJ, "ppcr_radius.o"), cc + no_pk + [RADIUS_TU])]
     for m in TILE_WIDTHS:
         jobs.append((os.path.join(OBJ, "ppcr_nn_tile_m%d.o" % m), cc + ["-DPPCR_TILE_M=%d" % m, TILE_TU]))
     return [(obj, cmd + ["-o", obj]) for obj, cmd in jobs]

@@ -33,6 +33,7 @@
 #include "ppcr_nn_tile_launch.hip.h"
 #include "ppcr_score.hip.h"
 #include "ppcr_refine.hip.h"
+#include "ppcr_radius.hip.h"
 
 using namespace ppcr;
 using namespace ppcr::dev;
@@ -63,13 +64,15 @@ enum KernelId {
     K_INNER,
     K_TRACK,
     K_NN_WIDE,
+    K_RADIUS,
     K_NUM
 };
 const char *const kKernelNames[K_NUM] = {
     "repack_kernel",   "bbox_kernel",    "cell_key_kernel",   "radix_sort",       "gather_points_kernel",
     "cell_start_kernel", "nn_fast_kernel", "nn_tile_cleanup_kernel", "nn_count_kernel",  "nn_scan",          "nn_fill_kernel",
     "nn_select_kernel", "csr_compact_kernel", "ell_count_sum_kernel", "weights_kernel", "accumulate_kernel",
-    "reduce_partials_kernel", "transform_kernel", "inner_steps_kernel", "track_kernel", "nn_wide_kernel"};
+    "reduce_partials_kernel", "transform_kernel", "inner_steps_kernel", "track_kernel", "nn_wide_kernel",
+    "radius_moments_kernel"};
 
 constexpr int kMailboxRing = 4;    // mailbox / report slots; at most kMaxAhead iterations are ever in flight
 constexpr int kMaxAhead = 3;       // outer iterations ppcr_align may have enqueued beyond the last one the host has seen
@@ -272,6 +275,13 @@ struct ppcr_ctx {
     DevBuf<unsigned long long> gen_keys;
     DevBuf<unsigned long long> d_total;
     int64_t nnz = -1;
+    // unbounded radius search without an association (ppcr_hip_radius.inc): the per-block pair counts, and a target grid
+    // of its own (radius-sized cells) for handles whose grid is not a one-pass grid of the current radius
+    DevBuf<unsigned long long> rad_counts;
+    DevBuf<float4> rad_tgt;
+    DevBuf<int> rad_cell_start;
+    GridDesc rad_grid{};
+    double rad_grid_radius = -1;  // (< 0: none, or built for an earlier target)
 
     // reductions
     DevBuf<double> partials, d_sums;
@@ -375,3 +385,4 @@ void trace_print(ppcr_ctx *c)
 #include "ppcr_hip_batch.inc"      // ppcr_align_many, ppcr_batch_run
 #include "ppcr_hip_score.inc"      // ppcr_scorer: many candidate poses scored against a resident target
 #include "ppcr_hip_refine.inc"     // ppcr_scorer_refine: many candidate poses polished by fused search, weights and solve
+#include "ppcr_hip_radius.inc"     // unbounded radius iterations: moments without an association

@@ -141,6 +141,9 @@ int ppcr_destroy(ppcr_ctx *c)
     c->d_inner_ctl.release_idle();
     c->track_part.release_idle();
     c->track_ticket.release_idle();
+    c->rad_counts.release_idle();
+    c->rad_tgt.release_idle();
+    c->rad_cell_start.release_idle();
     pinned_pool(c->device).give(c->h_pinned);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -328,6 +331,7 @@ static int set_target_common(ppcr_ctx *c, const void *p, bool dev, int64_t n, in
     c->nt = n;
     c->have_tgt = true;
     c->grid_valid = false;
+    c->rad_grid_radius = -1;
     c->origin_valid = false;
     c->dm2_valid = false;
     c->assoc_space = 0;

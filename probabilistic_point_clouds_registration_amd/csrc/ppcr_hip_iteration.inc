@@ -920,10 +920,12 @@ int apply_transform_now(ppcr_ctx *c, const double T[12])
     return check_launch(c, "transform_kernel");
 }
 
-// IRLS on the current association (see ppcr_solve in ppcr.h): every half-step is K23 -> fold -> solve on the device;
-// the host only compares costs
-int solve_impl(ppcr_ctx *c, const double q0[4], const double t0[3], int max_steps, double f_tol, double T_out[12],
-               double cost_out[2], int *steps_out)
+// The IRLS loop both routes to the moments share: launch(R, t, ticket) enqueues the kernels that leave the partial moments
+// at that pose and the fold-and-solve step behind them (launch_step for a stored association, launch_radius_step for the
+// implicit unbounded one); the host only compares costs
+template <class Launch>
+int irls_loop(ppcr_ctx *c, const double q0[4], const double t0[3], int max_steps, double f_tol, double T_out[12],
+              double cost_out[2], int *steps_out, Launch &&launch)
 {
     const double qn = q0[0] * q0[0] + q0[1] * q0[1] + q0[2] * q0[2] + q0[3] * q0[3];
     if (!(qn > 0) || !std::isfinite(qn)) return fail(c, PPCR_ERR_INVALID, "initial rotation quaternion has zero or non-finite norm");
@@ -932,7 +934,7 @@ int solve_impl(ppcr_ctx *c, const double q0[4], const double t0[3], int max_step
     Vec3 t{{t0[0], t0[1], t0[2]}};
     StepTicket tk;
     StepResult res;
-    PPCR_TRY(launch_step(c, R, t.v, tk));
+    PPCR_TRY(launch(R, t.v, tk));
     PPCR_TRY(collect_step(c, tk, res));
     double cost_old = 0.5 * res.sums[16];
     cost_out[0] = cost_out[1] = cost_old;
@@ -949,7 +951,7 @@ int solve_impl(ppcr_ctx *c, const double q0[4], const double t0[3], int max_step
         if (res.degenerate || steps >= max_steps) break;
         // a decrease below the rounding floor of the moment-based cost (eps * (Sxx + Syy)) is no decrease
         if ((cost_old - fc) <= std::max(f_tol * cost_old, 1e-14 * 0.5 * (res.sums[17] + res.sums[18]))) break;
-        PPCR_TRY(launch_step(c, R, t.v, tk));
+        PPCR_TRY(launch(R, t.v, tk));
         PPCR_TRY(collect_step(c, tk, res));
         cost_old = 0.5 * res.sums[16];
     }
@@ -958,6 +960,14 @@ int solve_impl(ppcr_ctx *c, const double q0[4], const double t0[3], int max_step
     pack_T(R, t, T_out);
     if (steps_out) *steps_out = steps;
     return PPCR_OK;
+}
+
+// IRLS on the current association (see ppcr_solve in ppcr.h): every half-step is K23 -> fold -> solve on the device
+int solve_impl(ppcr_ctx *c, const double q0[4], const double t0[3], int max_steps, double f_tol, double T_out[12],
+               double cost_out[2], int *steps_out)
+{
+    return irls_loop(c, q0, t0, max_steps, f_tol, T_out, cost_out, steps_out,
+                     [c](const Mat3 &R, const double t[3], StepTicket &tk) { return launch_step(c, R, t, tk); });
 }
 
 }  // namespace
