@@ -232,6 +232,20 @@ int ppcr_batch_run(const ppcr_pair *pairs, int64_t n_pairs, const ppcr_batch_opt
  * unloading the library or to give the memory back; never required for correctness. */
 int ppcr_batch_release(void);
 
+/* Many small pairs, one launch: pair p is registered start to finish by one workgroup.  Same loop, same numbers (to
+ * rounding of the f64 sums) as ppcr_align on a handle per pair.  Limits: every cloud 1 .. PPCR_SMALL_MAX_POINTS points
+ * (16384), 0 < max_neighbours <= 20, n_iter >= 0, 1 <= inner_steps <= 100; anything else PPCR_ERR_INVALID, nothing run.
+ * history / costs / steps: NULL or n_pairs x n_iter x {12, 2, 1}, rows beyond n_iter_done[p] untouched.
+ * The search is brute force in LDS (no grid, no sort, no handle): the call for object tracks, scan segments and the leaves
+ * of a global search; pairs with larger clouds go to ppcr_batch_run (nothing is routed automatically).  The host packs all
+ * clouds into one pinned block; a batch is cut into launches whose packed clouds and per-pair scratch stay under
+ * PPCR_SMALL_BATCH_BYTES (256 MiB; the environment variable of that name, read at every call, lowers it for tests — a cut
+ * changes no pair's result), and the call synchronises once, at its end.  A pair's result depends on that pair alone. */
+#define PPCR_SMALL_MAX_POINTS 16384
+int ppcr_batch_run_small(const ppcr_pair *pairs, int64_t n_pairs, const ppcr_batch_options *opt, int device_id,
+                         double *T_all, int32_t *n_iter_done, double *history, double *costs, int32_t *steps,
+                         char *err, int64_t err_capacity);
+
 /* Device memory of the handles (no counterpart in the reference: its clouds live in host memory owned by PCL).
  * Every handle's buffers are blocks of a per-device pool: the library takes memory from the driver in a few large
  * slabs, sub-allocates them on the host side, and keeps what ppcr_destroy gives back for the next handle (at most

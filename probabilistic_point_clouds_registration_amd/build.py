@@ -31,7 +31,9 @@ DEPS = SOURCES + [os.path.join(CSRC, h) for h in ("ppcr_device.hip.h", "ppcr_ker
                                                   # the pose refinement on the same scorer
                                                   "ppcr_refine.hip.h", "ppcr_hip_refine.inc",
                                                   # unbounded radius iterations without an association
-                                                  "ppcr_radius.hip.h", "ppcr_hip_radius.inc")] + [
+                                                  "ppcr_radius.hip.h", "ppcr_hip_radius.inc",
+                                                  # batches of small pairs, one workgroup per pair (compiled with the C-ABI unit)
+                                                  "ppcr_small.hip.h", "ppcr_hip_small.inc")] + [
     os.path.join(ROOT, "include", "ppcr.h")]
 
 

@@ -34,6 +34,7 @@
 #include "ppcr_score.hip.h"
 #include "ppcr_refine.hip.h"
 #include "ppcr_radius.hip.h"
+#include "ppcr_small.hip.h"
 
 using namespace ppcr;
 using namespace ppcr::dev;
@@ -386,3 +387,4 @@ void trace_print(ppcr_ctx *c)
 #include "ppcr_hip_score.inc"      // ppcr_scorer: many candidate poses scored against a resident target
 #include "ppcr_hip_refine.inc"     // ppcr_scorer_refine: many candidate poses polished by fused search, weights and solve
 #include "ppcr_hip_radius.inc"     // unbounded radius iterations: moments without an association
+#include "ppcr_hip_small.inc"      // ppcr_batch_run_small: batches of small pairs, one workgroup per pair, one launch
