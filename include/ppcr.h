@@ -246,6 +246,21 @@ int ppcr_batch_run_small(const ppcr_pair *pairs, int64_t n_pairs, const ppcr_bat
                          double *T_all, int32_t *n_iter_done, double *history, double *costs, int32_t *steps,
                          char *err, int64_t err_capacity);
 
+/* ppcr_batch_run_small with a cell-grid search: same parameters, limits, error codes, outputs and launch cut.  What differs:
+ * - the search.  Every workgroup sorts its pair's target once into a uniform grid of its own (cell edge >= radius, at most
+ *   8192 cells, the edge enlarged for sparse targets until they fit) and a source row measures the 27 cells around it
+ *   instead of every target point: the call for the upper part of the size range (thousands of points per cloud);
+ * - the scratch.  Besides the stored winners a pair takes 16 * n_target + 12 * n_source bytes of device memory (the sorted
+ *   clouds) from the pool for the duration of the call; they count towards PPCR_SMALL_BATCH_BYTES, per pair
+ *   12 * (n_source + n_target) + 16 * n_target + 12 * n_source (+ 2 * max_neighbours * n_source with inner_steps > 1);
+ * - the bits.  The association is the same set of pairs with the same ties, but the rows are summed in cell order: results
+ *   equal ppcr_batch_run_small's to rounding of the f64 sums, not bit for bit.  They are reproducible, and a pair's result
+ *   depends on that pair alone.
+ * Nothing is routed between the two calls automatically. */
+int ppcr_batch_run_small_grid(const ppcr_pair *pairs, int64_t n_pairs, const ppcr_batch_options *opt, int device_id,
+                              double *T_all, int32_t *n_iter_done, double *history, double *costs, int32_t *steps,
+                              char *err, int64_t err_capacity);
+
 /* Device memory of the handles (no counterpart in the reference: its clouds live in host memory owned by PCL).
  * Every handle's buffers are blocks of a per-device pool: the library takes memory from the driver in a few large
  * slabs, sub-allocates them on the host side, and keeps what ppcr_destroy gives back for the next handle (at most

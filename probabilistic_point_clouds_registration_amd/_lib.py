@@ -24,7 +24,7 @@ SYMBOLS = [
     "ppcr_profile_get", "ppcr_set_option", "ppcr_batch_run", "ppcr_align_many", "ppcr_set_companion",
     "ppcr_get_companion", "ppcr_set_ground_truth", "ppcr_mse_ground_truth", "ppcr_mse_previous", "ppcr_voxel_filter",
     "ppcr_nearest_sq_distances", "ppcr_stop_rule_check", "ppcr_align_report", "ppcr_batch_release",
-    "ppcr_memory_stats", "ppcr_memory_trim", "ppcr_batch_run_small",
+    "ppcr_memory_stats", "ppcr_memory_trim", "ppcr_batch_run_small", "ppcr_batch_run_small_grid",
     "ppcr_scorer_create", "ppcr_scorer_set_source", "ppcr_scorer_score", "ppcr_scorer_last_search_ms",
     "ppcr_scorer_last_error", "ppcr_scorer_destroy",
     "ppcr_scorer_set_params", "ppcr_scorer_refine", "ppcr_scorer_last_refine_ms",
@@ -130,6 +130,7 @@ def load():
     L.ppcr_batch_run.argtypes = [C.POINTER(Pair), i64, C.POINTER(BatchOptions), C.POINTER(i32), i32, i32, vp, vp,
                                  C.c_char_p, i64]
     L.ppcr_batch_run_small.argtypes = [C.POINTER(Pair), i64, C.POINTER(BatchOptions), i32, vp, vp, vp, vp, vp, C.c_char_p, i64]
+    L.ppcr_batch_run_small_grid.argtypes = L.ppcr_batch_run_small.argtypes
     L.ppcr_align_many.argtypes = [C.POINTER(vp), i32, i32, i32, dbl, dbl, vp, vp, i32, dbl, vp, vp]
     L.ppcr_memory_stats.argtypes = [i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.ppcr_memory_trim.argtypes = [i32]
@@ -535,11 +536,15 @@ def batch_run(pairs, radius, max_neighbours, dof=5.0, n_iter=20, cost_drop_thres
 
 
 def batch_run_small(pairs, radius, max_neighbours, dof=5.0, n_iter=20, cost_drop_thresh=0.0, n_cost_drop_it=5,
-                    inner_steps=1, f_tol=1e-5, q0=(1, 0, 0, 0), t0=(0, 0, 0), device_id=0, dim=3, want_history=False):
-    """ppcr_batch_run_small: pairs = [(src, tgt), ...] host arrays of at most 16384 points each, every pair registered by one
+                    inner_steps=1, f_tol=1e-5, q0=(1, 0, 0, 0), t0=(0, 0, 0), device_id=0, dim=3, want_history=False,
+                    search="brute"):
+    """ppcr_batch_run_small, or with search="grid" ppcr_batch_run_small_grid (a cell grid per pair instead of the scan): pairs = [(src, tgt), ...] host arrays of at most 16384 points each, every pair registered by one
     workgroup of one launch -> ([n,3,4] final transforms, [n] iterations done); with want_history also a dict of history
     [n,n_iter,3,4], costs [n,n_iter,2] (NaN beyond a pair's iterations) and steps [n,n_iter] (0 there)."""
+    if search not in ("brute", "grid"):
+        raise ValueError('search is "brute" or "grid"')
     L = load()
+    run = L.ppcr_batch_run_small_grid if search == "grid" else L.ppcr_batch_run_small
     n = len(pairs)
     keep = [(_cloud(s), _cloud(t)) for s, t in pairs]
     arr = (Pair * max(n, 1))()
@@ -555,7 +560,7 @@ def batch_run_small(pairs, radius, max_neighbours, dof=5.0, n_iter=20, cost_drop
            "steps": np.zeros((n, rows), dtype=np.int32)} if want_history else None
     ptr = [rec[k].ctypes.data for k in ("history", "costs", "steps")] if want_history else [None] * 3
     err = C.create_string_buffer(512)
-    rc = L.ppcr_batch_run_small(arr, n, C.byref(opt), int(device_id), T.ctypes.data, done.ctypes.data, *ptr, err, 512)
+    rc = run(arr, n, C.byref(opt), int(device_id), T.ctypes.data, done.ctypes.data, *ptr, err, 512)
     if rc != 0:
         raise PpcrError(rc, err.value.decode())
     return (T, done, rec) if want_history else (T, done)

@@ -33,7 +33,9 @@ DEPS = SOURCES + [os.path.join(CSRC, h) for h in ("ppcr_device.hip.h", "ppcr_ker
                                                   # unbounded radius iterations without an association
                                                   "ppcr_radius.hip.h", "ppcr_hip_radius.inc",
                                                   # batches of small pairs, one workgroup per pair (compiled with the C-ABI unit)
-                                                  "ppcr_small.hip.h", "ppcr_hip_small.inc")] + [
+                                                  "ppcr_small.hip.h", "ppcr_hip_small.inc",
+                                                  # ... and their cell-grid variant
+                                                  "ppcr_small_grid.hip.h", "ppcr_hip_small_grid.inc")] + [
     os.path.join(ROOT, "include", "ppcr.h")]
 
 

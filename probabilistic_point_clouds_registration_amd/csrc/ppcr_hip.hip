@@ -35,6 +35,7 @@
 #include "ppcr_refine.hip.h"
 #include "ppcr_radius.hip.h"
 #include "ppcr_small.hip.h"
+#include "ppcr_small_grid.hip.h"
 
 using namespace ppcr;
 using namespace ppcr::dev;
@@ -388,3 +389,4 @@ void trace_print(ppcr_ctx *c)
 #include "ppcr_hip_refine.inc"     // ppcr_scorer_refine: many candidate poses polished by fused search, weights and solve
 #include "ppcr_hip_radius.inc"     // unbounded radius iterations: moments without an association
 #include "ppcr_hip_small.inc"      // ppcr_batch_run_small: batches of small pairs, one workgroup per pair, one launch
+#include "ppcr_hip_small_grid.inc" // ppcr_batch_run_small_grid: the same with a cell grid built inside the workgroup

@@ -1,6 +1,7 @@
 // Part of the translation unit ppcr_hip.hip: ppcr_batch_run_small — many small pairs, each registered start to finish by one
 // workgroup of one launch.  No handle, no grid, no sort: the host packs the clouds, copies them once, launches, copies the
-// records back and synchronises once.  Kernel: ppcr_small.hip.h.
+// records back and synchronises once.  Kernel: ppcr_small.hip.h.  small_batch_run is the host side of both small-batch
+// calls; ppcr_batch_run_small_grid (ppcr_hip_small_grid.inc) runs it with its own descriptor, scratch and kernel.
 
 // Bytes of one launch's packed clouds plus stored winners: a batch is cut into launches that stay under it (next to the
 // scorer's PPCR_SCORE_D2_BYTES).  Tests lower it through the environment variable PPCR_SMALL_BATCH_BYTES, read at every
@@ -36,10 +37,26 @@ void small_launch(const SmallArgs &a, unsigned n, hipStream_t stream)
     else small_align_kernel<M, -1><<<n, kBlock, 0, stream>>>(a);
 }
 
+// What the two small-batch entry points differ in (small_batch_run below is everything they share): the descriptor of a
+// pair, the device scratch a pair needs besides its stored winners, and the launch.  The other route: ppcr_hip_small_grid.inc.
+struct SmallBrute {
+    typedef SmallPair Desc;
+    static constexpr const char *name = "ppcr_batch_run_small", *kernel = "small_align_kernel";
+    static SmallPair &base(Desc &d) { return d; }
+    static size_t scratch_bytes(int64_t, int64_t) { return 0; }
+    static void describe(Desc &, const float *, const float *, double, size_t) {}
+    static void launch(SmallArgs &a, const Desc *pairs, void *, unsigned n, hipStream_t stream)
+    {
+        a.pairs = pairs;
+        if (a.m <= 10) small_launch<10>(a, n, stream);
+        else small_launch<20>(a, n, stream);
+    }
+};
+
 // the memory of one call: taken from the pools, given back when the call returns (the stream is idle by then)
 struct SmallBlocks {
     int device;
-    void *pinned = nullptr, *dev_in = nullptr, *dev_nbr = nullptr, *dev_out = nullptr;
+    void *pinned = nullptr, *dev_in = nullptr, *dev_nbr = nullptr, *dev_out = nullptr, *dev_scratch = nullptr;
     explicit SmallBlocks(int d) : device(d) {}
     ~SmallBlocks()
     {
@@ -47,37 +64,37 @@ struct SmallBlocks {
         device_pool(device).free(dev_in);
         device_pool(device).free(dev_nbr);
         device_pool(device).free(dev_out);
+        device_pool(device).free(dev_scratch);
     }
 };
 
 inline size_t small_round(size_t v) { return (v + 255) / 256 * 256; }
 
-}  // namespace
-
-extern "C" {
-
-int ppcr_batch_run_small(const ppcr_pair *pairs, int64_t n_pairs, const ppcr_batch_options *opt, int device_id, double *T_all,
-                         int32_t *n_iter_done, double *history, double *costs, int32_t *steps, char *err, int64_t err_capacity)
+template <class Route>
+int small_batch_run(const ppcr_pair *pairs, int64_t n_pairs, const ppcr_batch_options *opt, int device_id, double *T_all,
+                    int32_t *n_iter_done, double *history, double *costs, int32_t *steps, char *err, int64_t err_capacity)
 {
+    typedef typename Route::Desc Desc;
+    const std::string who = Route::name;
     auto report = [&](int code, const std::string &msg) {
         if (err && err_capacity > 0) std::snprintf(err, (size_t)err_capacity, "%s", msg.c_str());
         return fail(nullptr, code, msg);
     };
     if (err && err_capacity > 0) err[0] = 0;
-    if (n_pairs < 0 || !opt) return report(PPCR_ERR_INVALID, "ppcr_batch_run_small: bad argument");
-    if (!(opt->radius > 0) || !std::isfinite(opt->radius)) return report(PPCR_ERR_INVALID, "ppcr_batch_run_small: radius must be positive and finite");
+    if (n_pairs < 0 || !opt) return report(PPCR_ERR_INVALID, who + ": bad argument");
+    if (!(opt->radius > 0) || !std::isfinite(opt->radius)) return report(PPCR_ERR_INVALID, who + ": radius must be positive and finite");
     if (opt->max_neighbours <= 0 || opt->max_neighbours > 20)
-        return report(PPCR_ERR_INVALID, "ppcr_batch_run_small: 0 < max_neighbours <= 20 (no unbounded search)");
-    if (!(opt->dof > 0) || opt->dim <= 0) return report(PPCR_ERR_INVALID, "ppcr_batch_run_small: dof and dim must be > 0");
-    if (opt->n_iter < 0) return report(PPCR_ERR_INVALID, "ppcr_batch_run_small: n_iter must be >= 0");
-    if (opt->inner_steps < 1 || opt->inner_steps > 100) return report(PPCR_ERR_INVALID, "ppcr_batch_run_small: 1 <= inner_steps <= 100");
+        return report(PPCR_ERR_INVALID, who + ": 0 < max_neighbours <= 20 (no unbounded search)");
+    if (!(opt->dof > 0) || opt->dim <= 0) return report(PPCR_ERR_INVALID, who + ": dof and dim must be > 0");
+    if (opt->n_iter < 0) return report(PPCR_ERR_INVALID, who + ": n_iter must be >= 0");
+    if (opt->inner_steps < 1 || opt->inner_steps > 100) return report(PPCR_ERR_INVALID, who + ": 1 <= inner_steps <= 100");
     {
         const double *q = opt->q0, qn = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
         if (!(qn > 0) || !std::isfinite(qn))
-            return report(PPCR_ERR_INVALID, "ppcr_batch_run_small: initial rotation quaternion has zero or non-finite norm");
+            return report(PPCR_ERR_INVALID, who + ": initial rotation quaternion has zero or non-finite norm");
     }
     if (n_pairs == 0) return PPCR_OK;
-    if (!pairs || !T_all) return report(PPCR_ERR_INVALID, "ppcr_batch_run_small: null pairs/T_all");
+    if (!pairs || !T_all) return report(PPCR_ERR_INVALID, who + ": null pairs/T_all");
     for (int64_t p = 0; p < n_pairs; p++) {
         const ppcr_pair &pr = pairs[p];
         if (pr.n_source < 1 || pr.n_source > PPCR_SMALL_MAX_POINTS || pr.n_target < 1 || pr.n_target > PPCR_SMALL_MAX_POINTS)
@@ -91,7 +108,7 @@ int ppcr_batch_run_small(const ppcr_pair *pairs, int64_t n_pairs, const ppcr_bat
         (void)hipGetLastError();
         return report(PPCR_ERR_NODEVICE, "no HIP device visible: this library has no CPU fallback");
     }
-    if (device_id < 0 || device_id >= visible) return report(PPCR_ERR_INVALID, "ppcr_batch_run_small: device id out of range");
+    if (device_id < 0 || device_id >= visible) return report(PPCR_ERR_INVALID, who + ": device id out of range");
 #define SMALL_HIP(expr)                                                                                       \
     do {                                                                                                      \
         const hipError_t e_ = (expr);                                                                         \
@@ -118,20 +135,25 @@ int ppcr_batch_run_small(const ppcr_pair *pairs, int64_t n_pairs, const ppcr_bat
     struct Launch {
         int64_t first, count;
         size_t floats, nbr, in_at;  // packed floats, stored winners (u16), where its input starts in the pinned block
+        size_t scratch;             // the route's device scratch in bytes, every pair's share a multiple of 16
     };
     std::vector<Launch> launches;
-    size_t in_total = 0, in_max = 0, nbr_max = 0;
+    size_t in_total = 0, in_max = 0, nbr_max = 0, scratch_max = 0;
     for (int64_t p = 0; p < n_pairs;) {
-        Launch l{p, 0, 0, 0, in_total};
+        Launch l{p, 0, 0, 0, in_total, 0};
+        size_t counted = 0;  // the bytes the cap is about: packed clouds, stored winners, scratch as the header states it
         while (p < n_pairs) {
             const size_t f = 3 * (size_t)(pairs[p].n_source + pairs[p].n_target), w = inner ? (size_t)m * (size_t)pairs[p].n_source : 0;
-            if (l.count > 0 && (long long)(4 * (l.floats + f) + 2 * (l.nbr + w)) > cap) break;
-            l.floats += f, l.nbr += w, l.count++, p++;
+            const size_t x = Route::scratch_bytes(pairs[p].n_source, pairs[p].n_target);
+            if (l.count > 0 && (long long)(counted + 4 * f + 2 * w + x) > cap) break;
+            counted += 4 * f + 2 * w + x;
+            l.floats += f, l.nbr += w, l.scratch += (x + 15) / 16 * 16, l.count++, p++;
         }
-        const size_t bytes = small_round((size_t)l.count * sizeof(SmallPair)) + small_round(4 * l.floats);
+        const size_t bytes = small_round((size_t)l.count * sizeof(Desc)) + small_round(4 * l.floats);
         in_total += bytes;
         in_max = std::max(in_max, bytes);
         nbr_max = std::max(nbr_max, l.nbr);
+        scratch_max = std::max(scratch_max, l.scratch);
         launches.push_back(l);
     }
     // the records of the whole batch, one block: T, history, costs (f64), then steps, n_iter_done (i32)
@@ -145,6 +167,7 @@ int ppcr_batch_run_small(const ppcr_pair *pairs, int64_t n_pairs, const ppcr_bat
     SMALL_HIP(device_pool(device_id).alloc(in_max, &mem.dev_in));
     if (inner) SMALL_HIP(device_pool(device_id).alloc(nbr_max * 2, &mem.dev_nbr));
     SMALL_HIP(device_pool(device_id).alloc(out_bytes, &mem.dev_out));
+    if (scratch_max > 0) SMALL_HIP(device_pool(device_id).alloc(scratch_max, &mem.dev_scratch));
     char *const h_in = static_cast<char *>(mem.pinned), *const h_out = h_in + in_total;
     double *const d_f64 = static_cast<double *>(mem.dev_out);
     int *const d_i32 = reinterpret_cast<int *>(static_cast<char *>(mem.dev_out) + small_round(n_f64 * 8));
@@ -181,13 +204,13 @@ int ppcr_batch_run_small(const ppcr_pair *pairs, int64_t n_pairs, const ppcr_bat
     for (size_t li = 0; li < launches.size(); li++) {
         const Launch &l = launches[li];
         // pack: the descriptors, then every pair's source and target as xyz, honouring the strides; the box of the target on the way
-        SmallPair *const desc = reinterpret_cast<SmallPair *>(h_in + l.in_at);
-        const size_t desc_bytes = small_round((size_t)l.count * sizeof(SmallPair));
+        Desc *const desc = reinterpret_cast<Desc *>(h_in + l.in_at);
+        const size_t desc_bytes = small_round((size_t)l.count * sizeof(Desc));
         float *const fl = reinterpret_cast<float *>(h_in + l.in_at + desc_bytes);
-        size_t at = 0, nbr_at = 0;
+        size_t at = 0, nbr_at = 0, scratch_at = 0;
         for (int64_t k = 0; k < l.count; k++) {
             const ppcr_pair &pr = pairs[l.first + k];
-            SmallPair &d = desc[k];
+            SmallPair &d = Route::base(desc[k]);
             d.ns = (int)pr.n_source, d.nt = (int)pr.n_target;
             d.src_off = at;
             const char *s = reinterpret_cast<const char *>(pr.source);
@@ -205,15 +228,15 @@ int ppcr_batch_run_small(const ppcr_pair *pairs, int64_t n_pairs, const ppcr_bat
             for (int x = 0; x < 3; x++) d.c[x] = 0.5 * ((double)lo[x] + (double)hi[x]);
             d.nbr_off = nbr_at;
             if (inner) nbr_at += (size_t)m * (size_t)pr.n_source;
+            Route::describe(desc[k], lo, hi, opt->radius, scratch_at);
+            scratch_at += (Route::scratch_bytes(pr.n_source, pr.n_target) + 15) / 16 * 16;
         }
         const size_t bytes = desc_bytes + small_round(4 * l.floats);
         SMALL_HIP(hipMemcpyAsync(mem.dev_in, h_in + l.in_at, bytes, hipMemcpyHostToDevice, stream));
-        a.pairs = static_cast<const SmallPair *>(mem.dev_in);
         a.packed = reinterpret_cast<float *>(static_cast<char *>(mem.dev_in) + desc_bytes);
         a.first = l.first;
         if (g_trace) SMALL_HIP(hipEventRecord(ev[0], stream));
-        if (m <= 10) small_launch<10>(a, (unsigned)l.count, stream);
-        else small_launch<20>(a, (unsigned)l.count, stream);
+        Route::launch(a, static_cast<const Desc *>(mem.dev_in), mem.dev_scratch, (unsigned)l.count, stream);
         SMALL_HIP(hipGetLastError());
         if (g_trace) {  // (diagnostic runs only: a synchronisation per launch)
             SMALL_HIP(hipEventRecord(ev[1], stream));
@@ -227,7 +250,7 @@ int ppcr_batch_run_small(const ppcr_pair *pairs, int64_t n_pairs, const ppcr_bat
     SMALL_HIP(hipStreamSynchronize(stream));
 #undef SMALL_HIP
     if (g_trace) {
-        std::fprintf(stderr, "PPCR_TRACE small_align_kernel pairs=%lld launches=%zu device_ms=%.3f\n", (long long)n_pairs, launches.size(), kernel_ms);
+        std::fprintf(stderr, "PPCR_TRACE %s pairs=%lld launches=%zu device_ms=%.3f\n", Route::kernel, (long long)n_pairs, launches.size(), kernel_ms);
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);
     }
 
@@ -242,6 +265,16 @@ int ppcr_batch_run_small(const ppcr_pair *pairs, int64_t n_pairs, const ppcr_bat
         if (steps) std::memcpy(steps + at, h_i32 + o_steps + at, done * sizeof(int32_t));
     }
     return PPCR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppcr_batch_run_small(const ppcr_pair *pairs, int64_t n_pairs, const ppcr_batch_options *opt, int device_id, double *T_all,
+                         int32_t *n_iter_done, double *history, double *costs, int32_t *steps, char *err, int64_t err_capacity)
+{
+    return small_batch_run<SmallBrute>(pairs, n_pairs, opt, device_id, T_all, n_iter_done, history, costs, steps, err, err_capacity);
 }
 
 }  // extern "C"

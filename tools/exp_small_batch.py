@@ -1,9 +1,9 @@
-"""ppcr_batch_run_small against ppcr_batch_run (four lanes) on batches of small synthetic pairs: pairs per second of both routes,
-warm, and the largest disagreement of their final transforms.
+"""ppcr_batch_run_small, ppcr_batch_run_small_grid and ppcr_batch_run (four lanes) on batches of small synthetic pairs: pairs per
+second of the three routes, warm, and the largest disagreement of their final transforms.
 
     python tools/exp_small_batch.py [--shapes 2048x2000,512x8000] [--repeats 7]
 
-Both routes are settled with two untimed calls, then timed `repeats` times end to end (host packing / uploads included: the
+Every route is settled with two untimed calls, then timed `repeats` times end to end (host packing / uploads included: the
 caller's view); the median and the spread (min .. max) are printed.  r = 1, m = 10, dof 5, the default stopping rule.  With
 PPCR_TRACE=1 in the environment the library also prints the device time of the small-batch launches to stderr.
 """
@@ -38,12 +38,15 @@ def main():
         n_pairs, n = (int(v) for v in shape.split("x"))
         pairs = [synth.make_pair(n, cfg=2, pair=p % 64)[:2] for p in range(n_pairs)]
         (Ts, ds), ts = timed(lambda: _lib.batch_run_small(pairs, 1.0, 10), a.repeats)
+        (Tg, dg), tg = timed(lambda: _lib.batch_run_small(pairs, 1.0, 10, search="grid"), a.repeats)
         (Tb, db), tb = timed(lambda: _lib.batch_run(pairs, 1.0, 10, lanes_per_device=4), a.repeats)
-        ang = max(synth.rotation_angle(x[:, :3], y[:, :3]) for x, y in zip(Ts, Tb))
-        print("%d pairs of %d <-> %d: iterations equal %s, largest disagreement %.2e rad %.2e" % (
-            n_pairs, n, n, bool(np.array_equal(ds, db)), ang, np.abs(Ts[:, :, 3] - Tb[:, :, 3]).max()))
-        for name, t in (("batch_run_small", ts), ("batch_run, 4 lanes", tb)):
-            print("  %-20s median %8.1f ms (%.1f .. %.1f)  %9.0f pairs/s" % (
+        print("%d pairs of %d <-> %d" % (n_pairs, n, n))
+        for name, T, d in (("batch_run_small", Ts, ds), ("batch_run_small, grid", Tg, dg)):
+            ang = max(synth.rotation_angle(x[:, :3], y[:, :3]) for x, y in zip(T, Tb))
+            print("  %-22s against batch_run: iterations equal %s, largest disagreement %.2e rad %.2e" % (
+                name, bool(np.array_equal(d, db)), ang, np.abs(T[:, :, 3] - Tb[:, :, 3]).max()))
+        for name, t in (("batch_run_small", ts), ("batch_run_small, grid", tg), ("batch_run, 4 lanes", tb)):
+            print("  %-22s median %8.1f ms (%.1f .. %.1f)  %9.0f pairs/s" % (
                 name, 1e3 * np.median(t), 1e3 * t.min(), 1e3 * t.max(), n_pairs / np.median(t)))
         sys.stdout.flush()
 
